@@ -3,7 +3,13 @@
 configs[1], "C2") on MI355X, plus the categorization SDK lookup of Nanosim-H-like 75x long
 reads against the C2 export at [10,25] (configs[2], "C3"), with the CPU oracle timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-lookup]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu] [--no-lookup] ...]
+
+A plain run sets up the C2 reads on the device, warms up, times K steps, writes the outputs of the last
+timed step if --dump-outputs is given and prints the headline line.  Everything else the benchmark measures
+(the per-kernel breakdown and dominant-kernel roofline, the C3 categorization legs, the CLI pipelines, host
+ingest, the CPU baselines, the C4 shard, the N > 1 export and oracle parity) runs only with --full; the
+--no-* options trim a --full run.
 
 A step is one pass of the counting hot path over the resident reads: bin + per-file count +
 merge (hga_count_run), the specificity histogram (hga_count_spec_hist) and the sorted export
@@ -162,16 +168,64 @@ class Dist:
             self.dist.destroy_process_group()
 
 
-def count_step(ctx):
+def count_step(ctx, keep=None):
     ctx.count_run(2)
-    ctx.spec_hist(THRESHOLDS)
+    hist = ctx.spec_hist(THRESHOLDS)
+    if keep is not None:
+        keep["spec_hist"] = hist
     return ctx.select_device(LOWER, UPPER)
 
 
-def dist_count_step(ex):
+def dist_count_step(ex, keep=None):
     ex.count(2)
-    ex.spec_hist(THRESHOLDS)
+    hist = ex.spec_hist(THRESHOLDS)
+    if keep is not None:
+        keep["spec_hist"] = hist
     return ex.select_counts(LOWER, UPPER)
+
+
+DUMP_SAMPLE = 1 << 20   # rows kept of each per-row output (seeded): 4 arrays, 36 MB in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, ctx, ex, D, keep, n_sel, n_disc):
+    """--dump-outputs: what the last timed step computed, as float64 / float32 .npy files under `path`:
+    its return values (spec_hist, select_counts) and the results it left on the device for the caller to
+    fetch: the merged rows (hga_count_rows) and the [10,25] export with its flags (hga_count_select_ex, the
+    same selection over the same rows).  Per-row outputs are a fixed seeded sample of DUMP_SAMPLE rows (in
+    row order); totals.npy carries whole-array sums so a difference outside the sample still shows.  N > 1:
+    every rank takes part in the reads, rank 0 writes its view."""
+    keys, counts = ctx.rows()
+    if ex:
+        sel, flags = ex.select(LOWER, UPPER)
+    else:
+        sel, flags, _ = ctx.select(LOWER, UPPER)
+    if D.rank != 0:
+        return None
+    os.makedirs(path, exist_ok=True)
+
+    def sample(n, seed):
+        if n <= DUMP_SAMPLE:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(seed).choice(n, size=DUMP_SAMPLE, replace=False))
+
+    ri, si = sample(len(keys), DUMP_SEED), sample(len(sel), DUMP_SEED + 1)
+    m32 = np.uint64(0xFFFFFFFF)
+    out = {
+        "spec_hist": np.asarray(keep["spec_hist"], dtype=np.float64),
+        "select_counts": np.array([n_sel, n_disc], dtype=np.float64),
+        "rows_keys": keys[ri].astype(np.float64),        # 2k = 38 bits: exact in float64
+        "rows_counts": counts[ri].astype(np.float64),
+        "selected_keys": sel[si].astype(np.float64),
+        "selected_flags": flags[si].astype(np.float32),
+        "totals": np.array([len(keys), len(sel), int(flags.sum()), *(int(v) for v in counts.sum(axis=0, dtype=np.uint64)),
+                            int((keys & m32).sum(dtype=np.uint64)), int((keys >> np.uint64(32)).sum(dtype=np.uint64)),
+                            int((sel & m32).sum(dtype=np.uint64)), int((sel >> np.uint64(32)).sum(dtype=np.uint64))],
+                           dtype=np.float64),
+    }
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 KERNEL_BYTES = {
@@ -725,6 +779,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: per-kernel breakdown and roofline, C3 categorization, CLI "
+                         "pipelines, ingest, CPU baselines, C4 shard, N > 1 export and parity (the --no-* options "
+                         "below trim it)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-lookup", action="store_true")
     ap.add_argument("--no-ingest", action="store_true", help="skip the host FASTQ ingest leg")
@@ -732,6 +791,10 @@ def main():
     ap.add_argument("--no-check", action="store_true", help="N > 1: skip the oracle check of the exchanged count")
     ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("HGA_CPU_THREADS", "16")))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the headline step only
+        args.no_cpu = args.no_lookup = args.no_ingest = args.no_scale = args.no_check = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     D = Dist(args.gpus)
@@ -753,29 +816,31 @@ def main():
     if D.pg:
         import hga_dist
         ex = hga_dist.OwnerExchange(ctx)   # the library's RCCL communicator (hga_comm_init)
-    step = (lambda: dist_count_step(ex)) if ex else (lambda: count_step(ctx))
+    keep = {}   # the last step's histogram, for --dump-outputs
+    step = (lambda: dist_count_step(ex, keep)) if ex else (lambda: count_step(ctx, keep))
     for _ in range(args.warmup):
         step()
     if ex:   # this rank's own count (what its counting kernels process in a step: min 1, no exchange)
         ctx.count_run(1)
     st = ctx.count_stats()
     stats = {"bytes": st.bytes, "instances": st.instances, "rows": st.distinct_rows, "files": 2}
-    # 1) untimed profiled pass: per-kernel breakdown (events around every launch)
-    names = ("kc_init", "kc_bin1", "kc_layout", "kc_rebin", "kc_count", "kc_spec_hist", "kc_select",
-             *XCH_KERNELS, "radix_upsweep", "radix_downsweep", "bx_colscan", "bx_scatter", "radix_segsort", "scan")
-    ctx.profile(True)
-    ctx.profile_reset()
-    for _ in range(args.steps):
-        step()
-    kernels = {}
-    for name in names:
-        ms, n = ctx.profile_get(name)
-        if n:
-            kernels[name] = {"ms_total": ms, "launches": n, "ms_per_step": ms / args.steps}
-    dom = max(("kc_bin1", "kc_rebin", "kc_count"), key=lambda k: kernels.get(k, {}).get("ms_total", 0))
-    # 2) timed pass: HIP events only around the dominant kernel (no event overhead elsewhere)
-    ctx.profile_select([dom])
-    ctx.profile_reset()
+    kernels, dom = {}, None
+    if args.full:
+        # 1) untimed profiled pass: per-kernel breakdown (events around every launch)
+        names = ("kc_init", "kc_bin1", "kc_layout", "kc_rebin", "kc_count", "kc_spec_hist", "kc_select",
+                 *XCH_KERNELS, "radix_upsweep", "radix_downsweep", "bx_colscan", "bx_scatter", "radix_segsort", "scan")
+        ctx.profile(True)
+        ctx.profile_reset()
+        for _ in range(args.steps):
+            step()
+        for name in names:
+            ms, n = ctx.profile_get(name)
+            if n:
+                kernels[name] = {"ms_total": ms, "launches": n, "ms_per_step": ms / args.steps}
+        dom = max(("kc_bin1", "kc_rebin", "kc_count"), key=lambda k: kernels.get(k, {}).get("ms_total", 0))
+        # 2) timed pass: HIP events only around the dominant kernel (no event overhead elsewhere)
+        ctx.profile_select([dom])
+        ctx.profile_reset()
     D.barrier()
     ctx.sync()
     t0 = time.perf_counter()
@@ -788,18 +853,19 @@ def main():
     ms_step = dt_max / args.steps * 1e3
     inst_total = D.sum(float(st.instances))
     value = inst_total / (dt_max / args.steps)
-    dom_ms, dom_n = ctx.profile_get(dom)
-    ctx.profile_select([])
-    ctx.profile(False)
-    per_step_launches = dom_n / args.steps
-    avg_launch_ms = dom_ms / dom_n
-    bytes_step = KERNEL_BYTES[dom](stats)
-    bytes_launch = bytes_step / per_step_launches
-    achieved = bytes_launch / (avg_launch_ms * 1e-3) / 1e9
-    traffic = pmc_traffic(dom)
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "algorithmic_bytes_per_launch": int(bytes_launch), "avg_launch_ms": round(avg_launch_ms, 4)}
+    if args.full:
+        dom_ms, dom_n = ctx.profile_get(dom)
+        ctx.profile_select([])
+        ctx.profile(False)
+        per_step_launches = dom_n / args.steps
+        avg_launch_ms = dom_ms / dom_n
+        bytes_step = KERNEL_BYTES[dom](stats)
+        bytes_launch = bytes_step / per_step_launches
+        achieved = bytes_launch / (avg_launch_ms * 1e-3) / 1e9
+        traffic = pmc_traffic(dom)
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "algorithmic_bytes_per_launch": int(bytes_launch), "avg_launch_ms": round(avg_launch_ms, 4)}
     # SURVEY.md §8(d) whole-counting model: 16.25 B per k-mer instance over the step time
     pipe_gbs = 16.25 * st.instances / (ms_step * 1e-3) / 1e9
     result = {
@@ -816,12 +882,16 @@ def main():
                                 f"{'RCCL (hga_comm_init)' if os.environ.get('HGA_BENCH_BACKEND', 'nccl') == 'nccl' else 'the host transport hook (gloo)'} "
                                 f"of {'packed u64 row pieces' if ctx.count_pack_bits() else '(key, counts[F]) rows'}")
                    if ex else None},
-        "roofline": roofline,
+        "full": args.full,
         "pipeline_roofline": {"model": "16.25 B per k-mer instance (SURVEY.md §8(d))",
                               "achieved": round(pipe_gbs, 1), "frac": round(pipe_gbs / HBM_PEAK_GBS, 4)},
-        "kernels_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in kernels.items()},
     }
-    if ex:   # the full export of the last timed step in code order, to one writer
+    if args.full:
+        result["roofline"] = roofline
+        result["kernels_ms_per_step"] = {k: round(v["ms_per_step"], 4) for k, v in kernels.items()}
+    if args.dump_outputs:   # the state the last timed step left, before any other leg touches it
+        result["dumped"] = dump_outputs(args.dump_outputs, ctx, ex, D, keep, n_sel, n_disc)
+    if ex and args.full:   # the full export of the last timed step in code order, to one writer
         ctx.comm_set_root(0)
         D.barrier()
         t1 = time.perf_counter()

@@ -3,16 +3,16 @@
 # usage (repo root on the box): bash tools/gpu_check.sh <tag> [test files...]
 #   (no test files = the whole -m gpu suite)
 TAG=$1; shift
-mkdir -p gpurun_out
+OUT=${HGA_OUT:-bench_out}; mkdir -p $OUT   # HGA_OUT: output folder, relative to the repo root
 if [ $# -gt 0 ]; then T="$*"; else T="tests -m gpu"; fi
-timeout -k 10 600 python -u -m pytest $T -x -q --timeout 120 --timeout-method thread > gpurun_out/pytest_$TAG.log 2>&1
+timeout -k 10 600 python -u -m pytest $T -x -q --timeout 120 --timeout-method thread > $OUT/pytest_$TAG.log 2>&1
 rc=$?
-tail -5 gpurun_out/pytest_$TAG.log
+tail -5 $OUT/pytest_$TAG.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -5 gpurun_out/bench_$TAG.err; exit 1; }
-python3 - "$TAG" <<'EOF'
+timeout -k 10 400 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -5 $OUT/bench_$TAG.err; exit 1; }
+python3 - "$OUT/bench_$TAG.json" <<'EOF'
 import json, sys
-d = json.load(open(f"gpurun_out/bench_{sys.argv[1]}.json"))
+d = json.load(open(sys.argv[1]))
 print("count: ms/step", d["ms_per_step"], "G k-mers/s", round(d["value"] / 1e9, 2), "roofline", d["roofline"]["kernel"],
       d["roofline"]["frac"])
 print("kernels", d["kernels_ms_per_step"])
