@@ -140,6 +140,11 @@ hga_status hga_connections_fetch_range(hga_ctx* c, uint64_t first, uint64_t coun
     HGA_CTX_GUARD(c, hga::connections_fetch(c, x, y, score, is_good, first, count));
 }
 
+hga_status hga_read_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap,
+                             uint32_t* shared) {
+    HGA_CTX_GUARD(c, hga::read_overlaps(c, x, y, n, overlap, shared));
+}
+
 hga_status hga_count_add_rows(hga_ctx* c, uint32_t file, const uint64_t* keys, const uint32_t* counts,
                               uint64_t n) {
     HGA_CTX_GUARD(c, hga::count_add_rows(c, file, keys, counts, n));

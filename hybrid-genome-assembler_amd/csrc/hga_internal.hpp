@@ -212,6 +212,11 @@ struct ConnState {
         lst;
 };
 
+// hga_read_overlaps' scratch (overlap.hip): the pairs and the two results of one chunk
+struct OverlapState {
+    DevBuf x, y, ov, sh;
+};
+
 // Multi-GPU transport of one rank (comm.hip): RCCL over xGMI, or a caller's host-staged hook.
 struct Comm {
     int rank = 0, nranks = 1;
@@ -249,6 +254,7 @@ struct hga_ctx {
     hga::CountState count;
     hga::LookupState lookup;
     hga::ConnState conn;
+    hga::OverlapState overlap;
     hga::PinnedBuf pinned;   // small host<->device staging (see count_spec_hist)
     hga::PinnedBuf pinned_sel;   // count_select counters + top-digit histogram
     std::unique_ptr<hga::Comm> comm;   // hga_comm_init*: the count results become global
@@ -320,6 +326,8 @@ void connections_run(hga_ctx* c, const uint32_t* pivots, uint64_t n_piv, uint32_
                      const int32_t* categories, uint64_t* n_out);
 void connections_fetch(hga_ctx* c, uint32_t* x, uint32_t* y, uint64_t* score, uint8_t* is_good, uint64_t first = 0,
                        uint64_t count = ~0ull);
+// overlap.hip: approximate_read_overlap of n read pairs on the current lookup result
+void read_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap, uint32_t* shared);
 void count_add_rows(hga_ctx* c, uint32_t file, const uint64_t* keys, const uint32_t* counts, uint64_t n);
 int count_pack_bits(hga_ctx* c);
 uint64_t count_partition_packed(hga_ctx* c, const uint64_t* splitters, uint32_t n_own, uint64_t* out,

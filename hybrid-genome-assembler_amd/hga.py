@@ -91,6 +91,7 @@ HGA_SYMBOLS = {
     "hga_connections_run": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint32, C.c_uint64, _i32p, _u64p]),
     "hga_connections_fetch": (C.c_int, [_vp, _u32p, _u32p, _u64p, _u8p]),
     "hga_connections_fetch_range": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p, _u32p, _u64p, _u8p]),
+    "hga_read_overlaps": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _i32p, _u32p]),
     "hga_hll_registers": (C.c_int, [_vp, C.c_int, C.c_uint32, _u8p]),
     "hga_profile_enable": (C.c_int, [_vp, C.c_int]),
     "hga_profile_select": (C.c_int, [_vp, C.c_char_p]),
@@ -441,6 +442,17 @@ class Ctx:
                                               _p(sc, C.c_uint64), _p(g, C.c_uint8)))
         return x, y, sc, g
 
+    # ---- read overlaps (approximate_read_overlap on the lookup's first-occurrence lists)
+    def read_overlaps(self, x, y):
+        """(overlap int32[n], shared uint32[n]) of the ReadID pairs (x[i], y[i])."""
+        xv, yv = np.ascontiguousarray(x, np.uint32), np.ascontiguousarray(y, np.uint32)
+        if xv.shape != yv.shape or xv.ndim != 1:
+            raise ValueError("x and y must be one-dimensional and of equal length")
+        ov, sh = np.zeros(len(xv), np.int32), np.zeros(len(xv), np.uint32)
+        _ck(lib().hga_read_overlaps(self._h, _p(xv, C.c_uint32), _p(yv, C.c_uint32), len(xv), _p(ov, C.c_int32),
+                                    _p(sh, C.c_uint32)))
+        return ov, sh
+
     # ---- HyperLogLog auto-k (KmerAnalysis.cpp:15-56) on the reads of lookup_set_reads
     def hll_registers(self, k: int, b: int = 10):
         """hll::HyperLogLog(b) registers over every KmerIterator window (HyperLogLog.hpp:96-106)."""
@@ -636,6 +648,9 @@ CLUSTER_SYMBOLS = {
     "hgc_cluster": (C.c_int, [C.c_char_p, _u64p, _i32p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p, _u64p,
                               _u32p, _u32p, _u64p, _u32p, C.c_uint32, C.POINTER(ClusterConfig), C.c_int,
                               C.POINTER(_u32p), _u64p, C.POINTER(_u32p), C.POINTER(_vp)]),
+    "hgc_cluster_batched": (C.c_int, [C.c_char_p, _u64p, _i32p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p,
+                                      _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32, C.POINTER(ClusterConfig), C.c_int,
+                                      C.POINTER(_u32p), _u64p, C.POINTER(_u32p), C.POINTER(_vp), C.c_int, _u64p]),
     "hgc_union_find": (C.c_int, [_u32p, _u32p, _u64p, C.c_uint64, _u32p, C.c_uint64, C.c_int, C.c_int,
                                  C.POINTER(_u64p), C.POINTER(_u32p), _u64p, C.POINTER(_u64p), C.POINTER(_u32p)]),
     "hgc_spectral": (C.c_int, [_u32p, _u32p, _u64p, C.c_uint64, C.c_int, C.POINTER(_u64p), C.POINTER(_u32p), _u64p]),
@@ -708,10 +723,13 @@ def sym_eigen(a):
 
 
 def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None, debug=False, first_read_id=1,
-                 start=None, end=None):
+                 start=None, end=None, batched_overlaps=False, stats=None):
     """run_clustering after construct_indices on the host (no device state): (component ids,
     per-read component id (0 = none), log text).  start / end: the reads' simulator coordinates
-    (print_components' intervals under debug), None = 0."""
+    (print_components' intervals under debug), None = 0.
+    batched_overlaps: the tail stage takes its spanning-tree edge overlaps through the batched hook
+    (the device path's batching and eligibility rule) with hga_read_overlaps' semantics computed on
+    the host.  stats: a dict that receives "overlap_edges_batched" and "overlap_edges_host"."""
     L = cluster_lib()
     cfg = cfg or cluster_config()
     off = np.ascontiguousarray(offsets, np.uint64)
@@ -724,13 +742,17 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
     ni = C.c_uint64()
     st = None if start is None else np.ascontiguousarray(start, np.uint32)
     en = None if end is None else np.ascontiguousarray(end, np.uint32)
-    _cck(L.hgc_cluster(bases, _p(off, C.c_uint64), _p(cat, C.c_int32),
-                       None if st is None else _p(st, C.c_uint32), None if en is None else _p(en, C.c_uint32),
-                       n, avg_read_length, first_read_id,
-                       _p(a["hit_ptr"], C.c_uint64), _p(a["sorted_kid"], C.c_uint32), _p(a["first_ptr"], C.c_uint64),
-                       _p(a["first_kid"], C.c_uint32), _p(a["first_pos"], C.c_uint32), _p(a["kci_ptr"], C.c_uint64),
-                       _p(a["kci_read"], C.c_uint32), len(a["kci_ptr"]) - 1, C.byref(cfg), 1 if debug else 0,
-                       C.byref(ip), C.byref(ni), C.byref(op), C.byref(lp)))
+    ove = np.zeros(2, np.uint64)
+    _cck(L.hgc_cluster_batched(bases, _p(off, C.c_uint64), _p(cat, C.c_int32),
+                               None if st is None else _p(st, C.c_uint32), None if en is None else _p(en, C.c_uint32),
+                               n, avg_read_length, first_read_id,
+                               _p(a["hit_ptr"], C.c_uint64), _p(a["sorted_kid"], C.c_uint32), _p(a["first_ptr"], C.c_uint64),
+                               _p(a["first_kid"], C.c_uint32), _p(a["first_pos"], C.c_uint32), _p(a["kci_ptr"], C.c_uint64),
+                               _p(a["kci_read"], C.c_uint32), len(a["kci_ptr"]) - 1, C.byref(cfg), 1 if debug else 0,
+                               C.byref(ip), C.byref(ni), C.byref(op), C.byref(lp), 1 if batched_overlaps else 0,
+                               _p(ove, C.c_uint64)))
+    if stats is not None:
+        stats["overlap_edges_batched"], stats["overlap_edges_host"] = int(ove[0]), int(ove[1])
     ids = _take(ip, ni.value, np.uint32, L.hgc_free)
     owner = _take(op, n, np.uint32, L.hgc_free)
     log = C.string_at(lp.value).decode()

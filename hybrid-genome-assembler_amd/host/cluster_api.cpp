@@ -70,12 +70,16 @@ void hgc_free(void* p) { std::free(p); }
 // component ids (ascending; under debug in print_components' order), per read the id of the returned
 // component containing it (0 = none), the timing/log text (with print_components' blocks under debug).
 // start / end: the reads' simulator-header coordinates (GenomeReadData start / end), null = 0.
-int hgc_cluster(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
+// hgc_cluster_batched: the same with the tail stage's batched overlap hook (set_device_overlaps) set
+// to the engine's host implementation of hga_read_overlaps when batched != 0 — the device path's
+// batching and eligibility rule without a device; ov_edges[2] (may be null) receives the tail stage's
+// edge counts {from the batch, from the host's approximate_read_overlap}.
+int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
                 const uint32_t* end, uint64_t n_reads,
                 uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
                 const uint64_t* first_ptr, const uint32_t* first_kid, const uint32_t* first_pos, const uint64_t* kci_ptr,
                 const uint32_t* kci_read, uint32_t n_sdk, const hgc_config* cfg, int debug, uint32_t** ids_out,
-                uint64_t* n_ids, uint32_t** comp_of_read, char** log_out) {
+                uint64_t* n_ids, uint32_t** comp_of_read, char** log_out, int batched, uint64_t* ov_edges) {
     return guard([&] {
         hgah::RecordSet rs;
         rs.bases.append(bases, n_reads ? offsets[n_reads] : 0);
@@ -104,8 +108,16 @@ int hgc_cluster(const char* bases, const uint64_t* offsets, const int32_t* categ
                                  std::vector<uint32_t>(first_pos, first_pos + U),
                                  std::vector<uint64_t>(kci_ptr, kci_ptr + n_sdk + 1),
                                  std::vector<uint32_t>(kci_read, kci_read + HK), nullptr);
+        if (batched)
+            e.set_device_overlaps([&e](const std::vector<hgah::ComponentID>& x, const std::vector<hgah::ComponentID>& y) {
+                return e.host_read_overlaps(x, y);
+            });
         std::ostringstream log;
         const auto ids = e.run(log);
+        if (ov_edges) {
+            ov_edges[0] = e.overlap_edges_device();
+            ov_edges[1] = e.overlap_edges_host();
+        }
         std::vector<uint32_t> owner(n_reads, 0);
         for (auto id : ids)
             for (uint32_t r : e.components().at(id).reads) owner[r - first_read_id] = id;
@@ -115,6 +127,17 @@ int hgc_cluster(const char* bases, const uint64_t* offsets, const int32_t* categ
         const std::string s = log.str();
         *log_out = dup(s.c_str(), s.size() + 1);
     });
+}
+
+int hgc_cluster(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
+                const uint32_t* end, uint64_t n_reads,
+                uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
+                const uint64_t* first_ptr, const uint32_t* first_kid, const uint32_t* first_pos, const uint64_t* kci_ptr,
+                const uint32_t* kci_read, uint32_t n_sdk, const hgc_config* cfg, int debug, uint32_t** ids_out,
+                uint64_t* n_ids, uint32_t** comp_of_read, char** log_out) {
+    return hgc_cluster_batched(bases, offsets, category, start, end, n_reads, avg_read_length, first_read_id, hit_ptr,
+                               sorted_kid, first_ptr, first_kid, first_pos, kci_ptr, kci_read, n_sdk, cfg, debug, ids_out,
+                               n_ids, comp_of_read, log_out, 0, nullptr);
 }
 
 // union_find (ReadClusteringEngine.cpp:424-489) of an ordered connection list.

@@ -871,25 +871,42 @@ int ClusteringEngine::approximate_read_overlap(ComponentID x, ComponentID y) con
     return std::max(max_x - min_x, max_y - min_y);
 }
 
-// get_spanning_tree_tails (:509-573).
-std::pair<std::vector<ComponentID>, std::vector<ComponentID>> ClusteringEngine::spanning_tree_tails(
-    const SpanningTree& tree) const {
-    std::map<ComponentID, std::map<ComponentID, int>> adjacency;
-    // the edges' overlaps (an intersection of two merged components' KmerID lists each: the stage's
-    // cost) on the host threads, then the adjacency built in tree order as before
-    std::vector<int> ov(tree.size());
-    {
-        const int T = std::max(1, std::min<int>(host_threads(), (int)(tree.size() / 8) + 1));
-        std::atomic<size_t> next{0};
-        auto work = [&] {
-            size_t q;
-            while ((q = next.fetch_add(1)) < tree.size()) ov[q] = approximate_read_overlap(tree[q].first, tree[q].second);
-        };
-        std::vector<std::thread> th;
-        for (int t = 1; t < T; ++t) th.emplace_back(work);
-        work();
-        for (auto& x : th) x.join();
+// hga_read_overlaps on the host: both reads' first-occurrence lists are distinct and ascending.
+std::vector<int> ClusteringEngine::host_read_overlaps(const std::vector<ComponentID>& x,
+                                                      const std::vector<ComponentID>& y) const {
+    if (x.size() != y.size()) throw std::invalid_argument("overlap pairs: x and y differ in length");
+    std::vector<int> out(x.size(), 0);
+    for (size_t q = 0; q < x.size(); ++q) {
+        const uint64_t rx = (uint64_t)x[q] - first_id_, ry = (uint64_t)y[q] - first_id_;
+        if (x[q] < first_id_ || y[q] < first_id_ || rx >= reads_.size() || ry >= reads_.size())
+            throw std::invalid_argument("overlap pairs: ReadID outside the reads");
+        uint64_t i = first_ptr_[rx], j = first_ptr_[ry];
+        const uint64_t ie = first_ptr_[rx + 1], je = first_ptr_[ry + 1];
+        int max_x = INT_MIN, max_y = INT_MIN, min_x = INT_MAX, min_y = INT_MAX;
+        bool any = false;
+        while (i < ie && j < je) {
+            if (first_kid_[i] < first_kid_[j]) {
+                ++i;
+            } else if (first_kid_[j] < first_kid_[i]) {
+                ++j;
+            } else {
+                const int px = (int)first_pos_[i++], py = (int)first_pos_[j++];
+                max_x = std::max(max_x, px);
+                min_x = std::min(min_x, px);
+                max_y = std::max(max_y, py);
+                min_y = std::min(min_y, py);
+                any = true;
+            }
+        }
+        if (any) out[q] = std::max(max_x - min_x, max_y - min_y);
     }
+    return out;
+}
+
+// get_spanning_tree_tails (:509-573); ov[q] = approximate_read_overlap of edge q (tree_overlaps).
+std::pair<std::vector<ComponentID>, std::vector<ComponentID>> ClusteringEngine::spanning_tree_tails(
+    const SpanningTree& tree, const std::vector<int>& ov) const {
+    std::map<ComponentID, std::map<ComponentID, int>> adjacency;
     for (size_t q = 0; q < tree.size(); ++q) {
         const auto& edge = tree[q];
         adjacency[edge.first].emplace(edge.second, ov[q]);
@@ -947,6 +964,84 @@ std::vector<ComponentID> ClusteringEngine::amplify_component(const std::vector<C
     return std::vector<ComponentID>(ids.begin(), ids.end());
 }
 
+// approximate_read_overlap of every spanning-tree edge of every tree (get_spanning_tree_tails' first
+// loop, :511-516: the stage's cost).  The edges between two components that were never merged into (at
+// most their own read: `kmers` is still that read's list) go in one batch to the hook, or to
+// hga_read_overlaps on the lookup's device-resident lists.  An edge touching a merge survivor (the
+// de-duplicated union of its members, absent positions reading as 0) keeps the host's
+// approximate_read_overlap, as does every edge without a device or under HGA_HOST_OVERLAPS=1; those run
+// on the host threads, all trees in one pool.
+std::vector<std::vector<int>> ClusteringEngine::tree_overlaps(
+    const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees) {
+    std::vector<std::vector<int>> ov(comps_and_trees.size());
+    for (size_t t = 0; t < ov.size(); ++t) ov[t].assign(comps_and_trees[t].second.size(), -1);   // -1: not computed yet
+    ov_edges_dev_ = ov_edges_host_ = 0;
+    const char* force_host = std::getenv("HGA_HOST_OVERLAPS");
+    if ((dev_ov_ || gpu_) && !(force_host && std::string(force_host) == "1")) {
+        std::vector<uint8_t> survivor(reads_.size(), 0);   // by read index: the component was merged into
+        for (auto& kv : index_)
+            if (kv.second.reads.size() > 1) survivor[kv.first - first_id_] = 1;
+        std::vector<ComponentID> bx, by;
+        std::vector<std::pair<size_t, size_t>> slot;   // (tree, edge) of each batched pair
+        for (size_t t = 0; t < ov.size(); ++t) {
+            const SpanningTree& tree = comps_and_trees[t].second;
+            for (size_t q = 0; q < tree.size(); ++q)
+                if (!survivor.at(tree[q].first - first_id_) && !survivor.at(tree[q].second - first_id_)) {
+                    bx.push_back(tree[q].first);
+                    by.push_back(tree[q].second);
+                    slot.emplace_back(t, q);
+                }
+        }
+        if (!bx.empty()) {
+            std::vector<int> got;
+            if (dev_ov_) {
+                got = dev_ov_(bx, by);
+                if (got.size() != bx.size()) throw std::runtime_error("device overlaps: wrong result count");
+            } else {
+                got.resize(bx.size());
+                if (hga_read_overlaps(gpu_, bx.data(), by.data(), bx.size(), got.data(), nullptr) != HGA_OK)
+                    throw std::runtime_error(std::string("hga_read_overlaps: ") + hga_last_error());
+            }
+            ++gpu_calls_;
+            for (size_t i = 0; i < slot.size(); ++i) {
+                if (got[i] < 0) throw std::runtime_error("device overlaps: negative overlap");
+                ov[slot[i].first][slot[i].second] = got[i];
+            }
+            ov_edges_dev_ = bx.size();
+        }
+    }
+    std::vector<std::pair<size_t, size_t>> todo;
+    for (size_t t = 0; t < ov.size(); ++t)
+        for (size_t q = 0; q < ov[t].size(); ++q)
+            if (ov[t][q] < 0) todo.emplace_back(t, q);
+    ov_edges_host_ = todo.size();
+    if (!todo.empty()) {
+        const int T = std::max(1, std::min<int>(host_threads(), (int)(todo.size() / 8) + 1));
+        std::atomic<size_t> next{0};
+        std::exception_ptr err;   // a worker's exception (index_.at, bad_alloc) is rethrown after the joins
+        std::mutex err_mu;
+        auto work = [&] {
+            try {
+                size_t i;
+                while ((i = next.fetch_add(1)) < todo.size()) {
+                    const auto& edge = comps_and_trees[todo[i].first].second[todo[i].second];
+                    ov[todo[i].first][todo[i].second] = approximate_read_overlap(edge.first, edge.second);
+                }
+            } catch (...) {
+                next.store(todo.size());   // the other workers stop at their next draw
+                std::lock_guard<std::mutex> g(err_mu);
+                if (!err) err = std::current_exception();
+            }
+        };
+        std::vector<std::thread> th;
+        for (int t = 1; t < T; ++t) th.emplace_back(work);
+        work();
+        for (auto& x : th) x.join();
+        if (err) std::rethrow_exception(err);
+    }
+    return ov;
+}
+
 // get_core_component_connections (:586-651).
 std::vector<Connection> ClusteringEngine::core_component_connections(
     const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees) {
@@ -955,9 +1050,13 @@ std::vector<Connection> ClusteringEngine::core_component_connections(
     using clk = std::chrono::steady_clock;
     double t_tree = 0, t_amp = 0, t_acc = 0;
     auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
-    for (auto& ct : comps_and_trees) {
-        auto t0 = clk::now();
-        const auto tails = spanning_tree_tails(ct.second);
+    auto t0 = clk::now();
+    const auto overlaps = tree_overlaps(comps_and_trees);
+    t_tree += since(t0);
+    for (size_t t = 0; t < comps_and_trees.size(); ++t) {
+        auto& ct = comps_and_trees[t];
+        t0 = clk::now();
+        const auto tails = spanning_tree_tails(ct.second, overlaps[t]);
         t_tree += since(t0);
         t0 = clk::now();
         const auto lv = amplify_component(tails.first, (Score)(int)cfg_.tail_amplification_min_score);
@@ -981,8 +1080,10 @@ std::vector<Connection> ClusteringEngine::core_component_connections(
     sort_connections(edges);
     if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1")
         std::fprintf(stderr, "hga-timing tails.spanning_tree_tails %.2f\nhga-timing tails.amplify %.2f\n"
-                             "hga-timing tails.accumulate %.2f\nhga-timing tails.intersections %.2f\n",
-                     t_tree, t_amp, t_acc, since(t_int0));
+                             "hga-timing tails.accumulate %.2f\nhga-timing tails.intersections %.2f\n"
+                             "hga-timing tails.overlap_edges_device %llu\nhga-timing tails.overlap_edges_host %llu\n",
+                     t_tree, t_amp, t_acc, since(t_int0), (unsigned long long)ov_edges_dev_,
+                     (unsigned long long)ov_edges_host_);
     return filter_connections(edges, [](const Connection& c) { return c.score > 0; });
 }
 

@@ -7,6 +7,10 @@
 // connection pass (get_all_connections / the filtered get_connections call at :750-755) runs on
 // the GPU (hga_connections_run) on the device-resident indices; every later get_connections
 // call works on merged components and the edited kmer_component_index and runs on the host.
+// The spanning-tree edge overlaps of the tail stage (approximate_read_overlap, :491-513) run on the
+// GPU too (hga_read_overlaps), in one batch over all trees, for the edges whose two endpoints were
+// never merged into: those components' KmerID lists are still the reads' own, which is what the
+// device's first-occurrence lists describe.  Edges touching a merge survivor stay on the host.
 //
 // Determinism: the reference iterates tsl::robin_map / std::unordered_map containers and sorts
 // connections with an unstable std::sort on the score only, so ties and container orders are
@@ -116,18 +120,33 @@ class ClusteringEngine {
     const std::map<ComponentID, Component>& components() const { return index_; }
     const std::vector<std::vector<ComponentID>>& kmer_component_index() const { return kci_; }
     bool used_gpu() const { return gpu_calls_ > 0; }
+    // Spanning-tree edges of the tail stage whose overlap came from the batch (device or hook) / from
+    // the host's approximate_read_overlap.
+    uint64_t overlap_edges_device() const { return ov_edges_dev_; }
+    uint64_t overlap_edges_host() const { return ov_edges_host_; }
     // Device connection pass over several ranks (categorization --gpus N): fn(pivots or empty for
     // "every read", min_score, min_kmers) -> connections in the reference order; replaces the
     // single-ctx call while the device indices describe the state.
     using DeviceConnections = std::function<std::vector<Connection>(const std::vector<ComponentID>&, Score, uint32_t)>;
     void set_device_connections(DeviceConnections fn) { dev_conn_ = std::move(fn); }
+    // Batched overlaps of the tail stage: fn(x, y) -> approximate_read_overlap of each ReadID pair
+    // (x[i], y[i]), both one-read components; replaces the single-ctx hga_read_overlaps call.
+    // HGA_HOST_OVERLAPS=1 in the environment keeps every edge on the host.
+    using DeviceOverlaps = std::function<std::vector<int>(const std::vector<ComponentID>& x, const std::vector<ComponentID>& y)>;
+    void set_device_overlaps(DeviceOverlaps fn) { dev_ov_ = std::move(fn); }
+    // hga_read_overlaps' semantics on the host, from the first-occurrence lists (the hook of the
+    // device-less tests): the intersection of the two reads' distinct KmerID lists.
+    std::vector<int> host_read_overlaps(const std::vector<ComponentID>& x, const std::vector<ComponentID>& y) const;
 
    private:
     std::vector<KmerID> accumulate_kmer_ids(const std::vector<ComponentID>& ids) const;
     uint32_t kmer_position(ComponentID read, KmerID kid) const;
     uint32_t read_length(ComponentID read) const;
     int approximate_read_overlap(ComponentID x, ComponentID y) const;
-    std::pair<std::vector<ComponentID>, std::vector<ComponentID>> spanning_tree_tails(const SpanningTree& tree) const;
+    // per tree, per edge: approximate_read_overlap (the batch where eligible, the host otherwise)
+    std::vector<std::vector<int>> tree_overlaps(const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees);
+    std::pair<std::vector<ComponentID>, std::vector<ComponentID>> spanning_tree_tails(const SpanningTree& tree,
+                                                                                      const std::vector<int>& ov) const;
     std::vector<ComponentID> amplify_component(const std::vector<ComponentID>& comp, Score min_score);
     std::vector<Connection> core_component_connections(
         const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees);
@@ -144,6 +163,8 @@ class ClusteringEngine {
     std::vector<std::vector<ComponentID>> kci_;
     hga_ctx* gpu_;
     DeviceConnections dev_conn_;
+    DeviceOverlaps dev_ov_;
+    uint64_t ov_edges_dev_ = 0, ov_edges_host_ = 0;
     bool pristine_ = true;   // no merge yet: the device indices still describe the state
     int gpu_calls_ = 0;
 };

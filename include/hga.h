@@ -320,6 +320,25 @@ hga_status hga_connections_fetch_range(hga_ctx* ctx, uint64_t first, uint64_t co
                                        uint64_t* score, uint8_t* is_good);
 
 /* ------------------------------------------------------------------------------
+ * Read overlaps — ReadClusteringEngine::approximate_read_overlap as get_spanning_tree_tails
+ * calls it per spanning-tree edge (src/clustering/ReadClusteringEngine.cpp:491-513), for n
+ * read pairs at once on the ctx's current lookup result (the rank's own reads, or the whole
+ * input's index after hga_lookup_gather).
+ * For ReadIDs x[i], y[i]: S = the KmerIDs both reads hit (the intersection of their distinct
+ * first_kid lists; the reference's multiset intersection pairs duplicates, which share one
+ * kmer_positions entry, so only the set matters).  shared[i] = |S|; overlap[i] = 0 if S is
+ * empty (max_element of an empty range there), else max(max - min of first_pos in x over S,
+ * max - min of first_pos in y over S).  x[i] == y[i] is allowed; the result is symmetric.
+ * ------------------------------------------------------------------------------ */
+
+/* x, y: host arrays of n ReadIDs in [first_read_id, first_read_id + n_reads), copied; any
+ *   other id: HGA_ERR_INVALID with nothing launched.  n == 0 is HGA_OK.
+ * overlap, shared: caller-allocated, n entries each; either may be NULL.
+ * Synchronous.  HGA_ERR_STATE before hga_lookup_run. */
+hga_status hga_read_overlaps(hga_ctx* ctx, const uint32_t* x, const uint32_t* y, uint64_t n,
+                             int32_t* overlap /* n, may be NULL */, uint32_t* shared /* n, may be NULL */);
+
+/* ------------------------------------------------------------------------------
  * Measurement: per-kernel device time, recorded with HIP events on the ctx stream.
  * ------------------------------------------------------------------------------ */
 hga_status hga_profile_enable(hga_ctx* ctx, int on);
