@@ -145,6 +145,44 @@ hga_status hga_read_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, u
     HGA_CTX_GUARD(c, hga::read_overlaps(c, x, y, n, overlap, shared));
 }
 
+hga_status hga_components_merge(hga_ctx* c, const uint64_t* group_ptr, const uint32_t* ids, uint64_t n_groups) {
+    HGA_CTX_GUARD(c, hga::components_merge(c, group_ptr, ids, n_groups));
+}
+
+hga_status hga_components_connections(hga_ctx* c, const uint32_t* pivots, uint64_t n_pivots, uint64_t min_score,
+                                      uint64_t* n) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(n, HGA_ERR_INVALID, "null out pointer");
+        HGA_REQUIRE(pivots || n_pivots == 0, HGA_ERR_INVALID, "null pivots with n_pivots > 0");
+        hga::components_connections(c, pivots, n_pivots, min_score, n);
+    });
+}
+
+hga_status hga_components_get_sizes(hga_ctx* c, hga_components_sizes* out) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(out, HGA_ERR_INVALID, "null out pointer");
+        hga::components_sizes(c, out);
+    });
+}
+
+hga_status hga_components_fetch_index(hga_ctx* c, uint64_t* ptr, uint32_t* ids) {
+    HGA_CTX_GUARD(c, hga::components_fetch_index(c, ptr, ids));
+}
+
+hga_status hga_components_fetch_kmers(hga_ctx* c, uint32_t id, uint32_t* kmers, uint64_t* n) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(n, HGA_ERR_INVALID, "null out pointer");
+        hga::components_fetch_kmers(c, id, kmers, n);
+    });
+}
+
+hga_status hga_components_reset(hga_ctx* c) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(c->lookup.ran, HGA_ERR_STATE, "hga_lookup_run not called");
+        hga::components_drop(c);
+    });
+}
+
 hga_status hga_count_add_rows(hga_ctx* c, uint32_t file, const uint64_t* keys, const uint32_t* counts,
                               uint64_t n) {
     HGA_CTX_GUARD(c, hga::count_add_rows(c, file, keys, counts, n));
@@ -320,6 +358,7 @@ hga_status hga_count_dump(hga_ctx* c, uint32_t file, uint64_t** keys, uint32_t**
 hga_status hga_lookup_load(hga_ctx* c, int k, const uint64_t* keys, uint32_t n) {
     HGA_CTX_GUARD(c, {
         HGA_REQUIRE(keys || n == 0, HGA_ERR_INVALID, "null keys");
+        hga::components_drop(c);
         hga::lookup_load(c, k, keys, n);
     });
 }
@@ -329,11 +368,17 @@ hga_status hga_lookup_set_reads(hga_ctx* c, const char* bases, const uint64_t* o
     HGA_CTX_GUARD(c, {
         HGA_REQUIRE(offsets, HGA_ERR_INVALID, "null offsets");
         HGA_REQUIRE(bases || offsets[n_reads] == 0, HGA_ERR_INVALID, "null bases");
+        hga::components_drop(c);
         hga::lookup_set_reads(c, bases, offsets, n_reads, first_read_id);
     });
 }
 
-hga_status hga_lookup_run(hga_ctx* c) { HGA_CTX_GUARD(c, hga::lookup_run(c)); }
+hga_status hga_lookup_run(hga_ctx* c) {
+    HGA_CTX_GUARD(c, {
+        hga::components_drop(c);
+        hga::lookup_run(c);
+    });
+}
 
 hga_status hga_lookup_get_sizes(hga_ctx* c, hga_lookup_sizes* out) {
     HGA_CTX_GUARD(c, {
@@ -431,7 +476,12 @@ hga_status hga_count_exchange(hga_ctx* c, uint32_t min_per_file) {
     HGA_CTX_GUARD(c, hga::count_exchange(c, min_per_file));
 }
 
-hga_status hga_lookup_gather(hga_ctx* c) { HGA_CTX_GUARD(c, hga::lookup_gather(c)); }
+hga_status hga_lookup_gather(hga_ctx* c) {
+    HGA_CTX_GUARD(c, {
+        hga::components_drop(c);
+        hga::lookup_gather(c);
+    });
+}
 
 hga_status hga_connections_gather(hga_ctx* c, uint64_t* n) {
     HGA_CTX_GUARD(c, {

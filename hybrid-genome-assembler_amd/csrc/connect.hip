@@ -1264,4 +1264,67 @@ void connections_fetch(hga_ctx* c, uint32_t* x, uint32_t* y, uint64_t* score, ui
     c->sync();
 }
 
+// The order and decode of connections_run's last stage for pairs a caller left densely in S.x / S.y / S.s
+// (components.hip): the one-pass composite key when it fits 64 bits, else the two-stage sort.
+void connections_order(hga_ctx* c, uint64_t n, uint32_t mxs, uint32_t ms) {
+    auto& L = c->lookup;
+    auto& S = c->conn;
+    S.n = 0;
+    S.ready = false;
+    if (n) {
+        HGA_REQUIRE(n < (1ull << 32), HGA_ERR_OOM, "too many connections for one sort");
+        const uint64_t nr = L.n_reads;
+        const int ib = std::max(1, bits_for(nr - 1));
+        const int sb = bits_for(mxs - ms);
+        // one region holding every pair: dense index i is slot i (cn_slot)
+        std::vector<uint64_t> rpre(CN_R + 1, n);
+        rpre[0] = 0;
+        uint64_t* d_rpre = static_cast<uint64_t*>(S.rpre.ensure((CN_R + 1) * 8));
+        HGA_HIP(hipMemcpyAsync(d_rpre, rpre.data(), (CN_R + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        uint32_t* ox = static_cast<uint32_t*>(S.ox.ensure(n * 4));
+        uint32_t* oy = static_cast<uint32_t*>(S.oy.ensure(n * 4));
+        uint64_t* os = static_cast<uint64_t*>(S.os.ensure(n * 8));
+        uint8_t* og = static_cast<uint8_t*>(S.og.ensure(n));
+        uint64_t* key = static_cast<uint64_t*>(S.key.ensure(n * 8));
+        const int32_t* no_cat = nullptr;
+        if (sb + 2 * ib <= 64) {
+            c->launch("cn_sort", [&] {
+                hipLaunchKernelGGL(cn_keys, dim3(cn_blocks(n, 256)), dim3(256), 0, c->stream, S.x.as<uint32_t>(),
+                                   S.y.as<uint32_t>(), S.s.as<uint32_t>(), d_rpre, n, n, mxs, ib, key);
+            });
+            c->check_launch("cn_keys");
+            radix_sort_u64(c, key, nullptr, n, sb + 2 * ib, L.scratch);
+            c->launch("cn_sort", [&] {
+                hipLaunchKernelGGL(cn_decode, dim3(cn_blocks(n, 256)), dim3(256), 0, c->stream, key, n, mxs, ib, no_cat,
+                                   L.first_read_id, ox, oy, os, og);
+            });
+            c->check_launch("cn_decode");
+        } else {
+            uint32_t* idx = static_cast<uint32_t*>(S.idx.ensure(n * 4));
+            uint32_t* sk = static_cast<uint32_t*>(S.skey.ensure(n * 4));
+            uint32_t* pos = static_cast<uint32_t*>(S.pos.ensure(n * 4));
+            c->launch("cn_sort", [&] {
+                hipLaunchKernelGGL(cn_pair_keys, dim3(cn_blocks(n, 256)), dim3(256), 0, c->stream, S.x.as<uint32_t>(),
+                                   S.y.as<uint32_t>(), d_rpre, n, n, ib, key, idx);
+            });
+            c->check_launch("cn_pair_keys");
+            radix_sort_u64(c, key, idx, n, 2 * ib, L.scratch);
+            c->launch("cn_sort", [&] {
+                hipLaunchKernelGGL(cn_score_keys, dim3(cn_blocks(n, 256)), dim3(256), 0, c->stream, S.s.as<uint32_t>(),
+                                   idx, n, mxs, sk, pos);
+            });
+            c->check_launch("cn_score_keys");
+            radix_sort_u32(c, sk, pos, n, sb, L.scratch);
+            c->launch("cn_sort", [&] {
+                hipLaunchKernelGGL(cn_decode2, dim3(cn_blocks(n, 256)), dim3(256), 0, c->stream, key, sk, pos, n, mxs, ib,
+                                   no_cat, L.first_read_id, ox, oy, os, og);
+            });
+            c->check_launch("cn_decode2");
+        }
+        c->sync();
+    }
+    S.n = n;
+    S.ready = true;
+}
+
 }  // namespace hga

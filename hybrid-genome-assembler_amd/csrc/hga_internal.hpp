@@ -11,6 +11,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <functional>
 #include <vector>
 
@@ -217,6 +218,24 @@ struct OverlapState {
     DevBuf x, y, ov, sh;
 };
 
+// The component view (components.hip): the state after merge_components calls, built lazily from the
+// current lookup result, whose own arrays it never writes.  kmer_component_index lists only shrink, so
+// they stay at the lookup's kci_ptr offsets in a copy of kci_val, with a current length per KmerID.  A
+// merge survivor's KmerID union lives in a grow-only pool; a per-read override (pool offset, length)
+// replaces the read's own sorted_kid slice.
+struct ComponentState {
+    bool live = false;
+    DevBuf idx, len;            // u32[H] copy of kci_val (read indices), u32[K] current list lengths
+    DevBuf pool;                // u32: the survivors' unions, appended merge by merge
+    DevBuf ovr_off, ovr_len;    // u64[n_reads] pool offset (~0: the read's own slice), u32[n_reads]
+    uint64_t pool_used = 0, pool_cap = 0;
+    std::vector<uint64_t> h_hit_ptr;                                      // host copy of hit_ptr
+    std::unordered_map<uint32_t, std::pair<uint64_t, uint32_t>> ovr;      // read index -> (pool offset, length)
+    uint64_t index_entries = 0, survivor_kmers = 0, merges = 0;
+    // scratch of one merge / one connections call
+    DevBuf mem, gk, rm, flag, ubuf, seg, ctr, work, rows, scratch;
+};
+
 // Multi-GPU transport of one rank (comm.hip): RCCL over xGMI, or a caller's host-staged hook.
 struct Comm {
     int rank = 0, nranks = 1;
@@ -255,6 +274,7 @@ struct hga_ctx {
     hga::LookupState lookup;
     hga::ConnState conn;
     hga::OverlapState overlap;
+    hga::ComponentState comp;
     hga::PinnedBuf pinned;   // small host<->device staging (see count_spec_hist)
     hga::PinnedBuf pinned_sel;   // count_select counters + top-digit histogram
     std::unique_ptr<hga::Comm> comm;   // hga_comm_init*: the count results become global
@@ -328,6 +348,17 @@ void connections_fetch(hga_ctx* c, uint32_t* x, uint32_t* y, uint64_t* score, ui
                        uint64_t count = ~0ull);
 // overlap.hip: approximate_read_overlap of n read pairs on the current lookup result
 void read_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap, uint32_t* shared);
+// connect.hip: orders the n pairs (x, y: read indices, s: score) a caller left in conn.x / conn.y / conn.s
+// as connections_run orders its own (score descending, then pivot, then candidate) and makes them the
+// result hga_connections_fetch reads, is_good = 0.  mxs: the largest score, ms: the smallest possible.
+void connections_order(hga_ctx* c, uint64_t n, uint32_t mxs, uint32_t ms);
+// components.hip: merge_components / get_connections on merged components (hga_components_*)
+void components_drop(hga_ctx* c);
+void components_merge(hga_ctx* c, const uint64_t* group_ptr, const uint32_t* ids, uint64_t n_groups);
+void components_connections(hga_ctx* c, const uint32_t* pivots, uint64_t n_piv, uint64_t min_score, uint64_t* n_out);
+void components_sizes(hga_ctx* c, hga_components_sizes* out);
+void components_fetch_index(hga_ctx* c, uint64_t* ptr, uint32_t* ids);
+void components_fetch_kmers(hga_ctx* c, uint32_t id, uint32_t* kmers, uint64_t* n);
 void count_add_rows(hga_ctx* c, uint32_t file, const uint64_t* keys, const uint32_t* counts, uint64_t n);
 int count_pack_bits(hga_ctx* c);
 uint64_t count_partition_packed(hga_ctx* c, const uint64_t* splitters, uint32_t n_own, uint64_t* out,

@@ -40,6 +40,11 @@ class LookupSizes(C.Structure):
                 ("firsts", C.c_uint64), ("reads_hit", C.c_uint64), ("n_sdk", C.c_uint32)]
 
 
+class ComponentsSizes(C.Structure):
+    _fields_ = [("index_entries", C.c_uint64), ("survivors", C.c_uint64), ("survivor_kmers", C.c_uint64),
+                ("merges", C.c_uint64)]
+
+
 class LookupResult(C.Structure):
     _fields_ = [("hit_ptr", _u64p), ("hit_kid", _u32p), ("hit_pos", _u32p), ("sorted_kid", _u32p),
                 ("first_ptr", _u64p), ("first_kid", _u32p), ("first_pos", _u32p),
@@ -92,6 +97,12 @@ HGA_SYMBOLS = {
     "hga_connections_fetch": (C.c_int, [_vp, _u32p, _u32p, _u64p, _u8p]),
     "hga_connections_fetch_range": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p, _u32p, _u64p, _u8p]),
     "hga_read_overlaps": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _i32p, _u32p]),
+    "hga_components_merge": (C.c_int, [_vp, _u64p, _u32p, C.c_uint64]),
+    "hga_components_connections": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint64, _u64p]),
+    "hga_components_get_sizes": (C.c_int, [_vp, C.POINTER(ComponentsSizes)]),
+    "hga_components_fetch_index": (C.c_int, [_vp, _u64p, _u32p]),
+    "hga_components_fetch_kmers": (C.c_int, [_vp, C.c_uint32, _u32p, _u64p]),
+    "hga_components_reset": (C.c_int, [_vp]),
     "hga_hll_registers": (C.c_int, [_vp, C.c_int, C.c_uint32, _u8p]),
     "hga_profile_enable": (C.c_int, [_vp, C.c_int]),
     "hga_profile_select": (C.c_int, [_vp, C.c_char_p]),
@@ -452,6 +463,45 @@ class Ctx:
         _ck(lib().hga_read_overlaps(self._h, _p(xv, C.c_uint32), _p(yv, C.c_uint32), len(xv), _p(ov, C.c_int32),
                                     _p(sh, C.c_uint32)))
         return ov, sh
+
+    # ---- merged components (merge_components / get_connections on the state merges leave)
+    def components_merge(self, groups):
+        """One merge_components call: groups is a list of ReadID lists, the first id of each survives."""
+        gp = np.zeros(len(groups) + 1, np.uint64)
+        gp[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64)
+        ids = np.ascontiguousarray([i for g in groups for i in g], np.uint32)
+        _ck(lib().hga_components_merge(self._h, _p(gp, C.c_uint64), _p(ids, C.c_uint32), len(groups)))
+
+    def components_connections(self, pivots, min_score: int = 1) -> int:
+        """get_connections of the pivots on the current component state; fetch with connections_range."""
+        pv = np.ascontiguousarray(pivots, np.uint32)
+        n = C.c_uint64()
+        _ck(lib().hga_components_connections(self._h, _p(pv, C.c_uint32), len(pv), min_score, C.byref(n)))
+        self._conn_n = n.value
+        return n.value
+
+    def components_sizes(self) -> ComponentsSizes:
+        s = ComponentsSizes()
+        _ck(lib().hga_components_get_sizes(self._h, C.byref(s)))
+        return s
+
+    def components_index(self):
+        """The current kmer_component_index as a CSR of ReadIDs: (ptr uint64[K + 1], ids uint32[entries])."""
+        ptr = np.zeros(self.lookup_sizes().n_sdk + 1, np.uint64)
+        ids = np.zeros(self.components_sizes().index_entries, np.uint32)
+        _ck(lib().hga_components_fetch_index(self._h, _p(ptr, C.c_uint64), _p(ids, C.c_uint32)))
+        return ptr, ids
+
+    def components_kmers(self, id: int):
+        """The current KmerID list of one id (uint32, ascending)."""
+        n = C.c_uint64()
+        _ck(lib().hga_components_fetch_kmers(self._h, id, None, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        _ck(lib().hga_components_fetch_kmers(self._h, id, _p(out, C.c_uint32), C.byref(n)))
+        return out
+
+    def components_reset(self):
+        _ck(lib().hga_components_reset(self._h))
 
     # ---- HyperLogLog auto-k (KmerAnalysis.cpp:15-56) on the reads of lookup_set_reads
     def hll_registers(self, k: int, b: int = 10):

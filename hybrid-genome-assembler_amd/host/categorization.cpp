@@ -148,23 +148,43 @@ int main(int argc, char* argv[]) {
     });
     hga_lookup_sizes sz;
     check(hga_lookup_get_sizes(ctx, &sz), "hga_lookup_get_sizes");
-    std::vector<uint64_t> hit_ptr(sz.n_reads + 1), first_ptr(sz.n_reads + 1), kci_ptr((size_t)sz.n_sdk + 1);
-    std::vector<uint32_t> sorted_kid(sz.hits), first_kid(sz.firsts), first_pos(sz.firsts), kci_read(sz.hits);
+    std::vector<uint64_t> hit_ptr(sz.n_reads + 1), first_ptr(sz.n_reads + 1), kci_ptr;
+    std::vector<uint32_t> sorted_kid(sz.hits), first_kid(sz.firsts), first_pos(sz.firsts), kci_read;
     hga_lookup_result res{};
     res.hit_ptr = hit_ptr.data();
     res.sorted_kid = sorted_kid.data();
     res.first_ptr = first_ptr.data();
     res.first_kid = first_kid.data();
     res.first_pos = first_pos.data();
-    res.kci_ptr = kci_ptr.data();
-    res.kci_read = kci_read.data();
+    // kmer_component_index stays on the device (hga_components_*) unless the engine keeps the host index
+    // (HGA_HOST_CONNECTIONS=1); the -d check and --index-out below read it back when they need it
+    const char* host_conn_env = std::getenv("HGA_HOST_CONNECTIONS");
+    const bool host_index = host_conn_env && std::string(host_conn_env) == "1";
+    bool have_kci = host_index;
+    if (host_index) {
+        kci_ptr.resize((size_t)sz.n_sdk + 1);
+        kci_read.resize(sz.hits);
+        res.kci_ptr = kci_ptr.data();
+        res.kci_read = kci_read.data();
+    }
     check(hga_lookup_fetch(ctx, &res), "hga_lookup_fetch");
+    auto need_kci = [&] {
+        if (have_kci) return;
+        kci_ptr.resize((size_t)sz.n_sdk + 1);
+        kci_read.resize(sz.hits);
+        hga_lookup_result r2{};
+        r2.kci_ptr = kci_ptr.data();
+        r2.kci_read = kci_read.data();
+        check(hga_lookup_fetch(ctx, &r2), "hga_lookup_fetch");
+        have_kci = true;
+    };
     const auto t1 = std::chrono::steady_clock::now();
     std::cout << "Index construction took "
               << std::chrono::duration_cast<std::chrono::milliseconds>(t1 - t0).count() << "ms\n";
     tm.mark("index_construction");
 
     if (engine_debug) {   // ReadClusteringEngine.cpp:285-297
+        need_kci();
         uint32_t discriminative = 0, total = 0;
         for (uint64_t id = 0; id < sz.n_sdk; ++id) {   // (the set of categories has one element iff all agree)
             const uint64_t a = kci_ptr[id], b = kci_ptr[id + 1];
@@ -181,6 +201,7 @@ int main(int argc, char* argv[]) {
     if (!index_out.empty()) {
         std::FILE* f = std::fopen(index_out.c_str(), "wb");
         if (!f) throw std::runtime_error("cannot write " + index_out);
+        need_kci();
         const uint64_t hdr[5] = {sz.n_reads, sz.hits, sz.firsts, sz.n_sdk, (uint64_t)k};
         std::fwrite(hdr, 8, 5, f);
         std::fwrite(hit_ptr.data(), 8, hit_ptr.size(), f);

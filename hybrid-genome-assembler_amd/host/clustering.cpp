@@ -538,9 +538,34 @@ ClusteringEngine::ClusteringEngine(const ClusteringConfig& cfg, bool debug, cons
     }
     // (built serially: the same construction on the host threads measured slower, 100 -> 155 ms at C3 —
     // 1.9 M small allocations contend in the allocator)
+    const char* host_conn = std::getenv("HGA_HOST_CONNECTIONS");
+    dev_comp_ = gpu_ && !(host_conn && std::string(host_conn) == "1");
+    if (dev_comp_) {   // the index stays on the device (hga_components_*)
+        hga_lookup_sizes sz;
+        if (hga_lookup_get_sizes(gpu_, &sz) != HGA_OK)
+            throw std::runtime_error(std::string("hga_lookup_get_sizes: ") + hga_last_error());
+        n_sdk_ = sz.n_sdk;
+        return;
+    }
     kci_.resize(kci_ptr.empty() ? 0 : kci_ptr.size() - 1);
     for (size_t k = 0; k + 1 < kci_ptr.size(); ++k)
         kci_[k].assign(kci_read.begin() + (int64_t)kci_ptr[k], kci_read.begin() + (int64_t)kci_ptr[k + 1]);
+    n_sdk_ = kci_.size();
+}
+
+const std::vector<std::vector<ComponentID>>& ClusteringEngine::kmer_component_index() const {
+    if (!dev_comp_) return kci_;
+    hga_components_sizes cs;
+    if (hga_components_get_sizes(gpu_, &cs) != HGA_OK)
+        throw std::runtime_error(std::string("hga_components_get_sizes: ") + hga_last_error());
+    std::vector<uint64_t> ptr(n_sdk_ + 1);
+    std::vector<uint32_t> ids(cs.index_entries);
+    if (hga_components_fetch_index(gpu_, ptr.data(), ids.data()) != HGA_OK)
+        throw std::runtime_error(std::string("hga_components_fetch_index: ") + hga_last_error());
+    kci_.assign(n_sdk_, {});
+    for (size_t k = 0; k < n_sdk_; ++k)
+        kci_[k].assign(ids.begin() + (int64_t)ptr[k], ids.begin() + (int64_t)ptr[k + 1]);
+    return kci_;
 }
 
 uint32_t ClusteringEngine::read_length(ComponentID r) const {   // ReadMetaData::length
@@ -603,7 +628,28 @@ std::vector<Connection> ClusteringEngine::get_connections(const std::vector<Comp
         if (keep_fraction >= 0) v.resize(std::min(v.size(), (size_t)((double)v.size() * keep_fraction)));
         return v;
     };
-    if (!(pristine_ && (gpu_ || dev_conn_))) return prefix(host_connections(pivots, min_score));
+    if (!pristine_ && dev_comp_) {   // merged components: the device's component state (components.hip)
+        std::vector<ComponentID> piv;
+        for (ComponentID p : pivots)
+            if (index_.count(p)) piv.push_back(p);   // (host_connections skips the others)
+        uint64_t n = 0;
+        if (hga_components_connections(gpu_, piv.data(), piv.size(), min_score, &n) != HGA_OK)
+            throw std::runtime_error(std::string("hga_components_connections: ") + hga_last_error());
+        if (keep_fraction >= 0) n = std::min<uint64_t>(n, (uint64_t)(size_t)((double)n * keep_fraction));
+        std::vector<uint32_t> x(n), y(n);
+        std::vector<uint64_t> s(n);
+        if (hga_connections_fetch_range(gpu_, 0, n, x.data(), y.data(), s.data(), nullptr) != HGA_OK)
+            throw std::runtime_error(std::string("hga_connections_fetch_range: ") + hga_last_error());
+        ++conn_dev_calls_;
+        std::vector<Connection> out(n);
+        // is_good compares the components' category sets (:319), which only the host holds
+        for (uint64_t i = 0; i < n; ++i) out[i] = {x[i], y[i], s[i], is_good(x[i], y[i])};
+        return out;
+    }
+    if (!(pristine_ && (gpu_ || dev_conn_))) {
+        if (!pristine_) ++conn_host_calls_;
+        return prefix(host_connections(pivots, min_score));
+    }
     if (min_kmers == 0 && pivots.empty()) return {};   // (a null pivot list means "every read" there)
     if (dev_conn_) {
         ++gpu_calls_;
@@ -648,16 +694,23 @@ std::vector<KmerID> ClusteringEngine::accumulate_kmer_ids(const std::vector<Comp
     return all;
 }
 
+static int& merge_call_no() {   // HGA_TIMING: merge calls are numbered over the process
+    static int call = 0;
+    return call;
+}
+
 // merge_components (:349-422).  Same statements, flat data structures: a survivor's KmerID union
 // is a mark pass over the dense KmerID range when the members hold many ids (a sort of the
 // concatenation otherwise), and the removal lists are a counting sort of (KmerID, component) pairs
 // by KmerID instead of an ordered map of vectors — on C3, where one component absorbs most reads
 // (~20 M pairs), the map took 17.8 s.  The kmer_component_index update runs over the host threads.
+// With the component state on the device (dev_comp_) the members, unions and categories are still
+// kept here, but the removal pairs and the index update are hga_components_merge's (components.hip).
 std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<ComponentList>& components) {
     using clk = std::chrono::steady_clock;
     const auto t_start = clk::now();
     std::vector<ComponentID> merged_ids;
-    const size_t nk = kci_.size();
+    const size_t nk = n_sdk_;
     const int HT = std::max(1, host_threads());
     // ranges [0, n) split over up to HT threads (the calling thread takes the last one)
     auto par = [&](size_t n, size_t grain, const std::function<void(int, size_t, size_t)>& f) {
@@ -676,6 +729,7 @@ std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<Co
     std::vector<std::vector<uint64_t>> pairs((size_t)HT);
     std::vector<uint8_t> mark;
     double t_members = 0, t_union = 0, t_pairs = 0;   // (HGA_TIMING parts of merge.groups)
+    bool any_merge = false;
     for (const ComponentList& ids : components) {
         if (ids.empty()) continue;   // (an empty spectral cluster would dereference ids[0] there)
         if (ids.size() == 1) {
@@ -722,7 +776,8 @@ std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<Co
         merged_ids.push_back(ids[0]);
         km[0] = &survivor.kmers;
         const auto q2 = clk::now();
-        par(ids.size(), 64, [&](int t, size_t a, size_t b) {
+        any_merge = true;
+        if (!dev_comp_) par(ids.size(), 64, [&](int t, size_t a, size_t b) {
             auto& pv = pairs[(size_t)t];
             size_t add = 0;
             for (size_t i = a; i < b; ++i) add += km[i]->size();
@@ -735,6 +790,27 @@ std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<Co
         t_members += std::chrono::duration<double, std::milli>(q1 - q0).count();
         t_union += std::chrono::duration<double, std::milli>(q2 - q1).count();
         t_pairs += std::chrono::duration<double, std::milli>(q3 - q2).count();
+    }
+    if (dev_comp_) {   // the removal pairs and the kmer_component_index edit: hga_components_merge
+        if (!any_merge) return merged_ids;
+        const auto t_groups = clk::now();
+        std::vector<uint64_t> gptr{0};
+        std::vector<uint32_t> gids;
+        for (const ComponentList& ids : components) {
+            gids.insert(gids.end(), ids.begin(), ids.end());
+            gptr.push_back(gids.size());
+        }
+        if (hga_components_merge(gpu_, gptr.data(), gids.data(), components.size()) != HGA_OK)
+            throw std::runtime_error(std::string("hga_components_merge: ") + hga_last_error());
+        if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1") {
+            auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+            const int call = ++merge_call_no();
+            std::fprintf(stderr,
+                         "hga-timing merge%d.groups %.2f\nhga-timing merge%d.members %.2f\nhga-timing merge%d.union %.2f\n"
+                         "hga-timing merge%d.device %.2f\n",
+                         call, ms(t_start, t_groups), call, t_members, call, t_union, call, ms(t_groups, clk::now()));
+        }
+        return merged_ids;
     }
     size_t npairs = 0;
     for (auto& pv : pairs) npairs += pv.size();
@@ -830,8 +906,7 @@ std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<Co
     for (auto& x : th) x.join();
     if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1") {
         auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        static int call = 0;   // one set of lines per call: merge<call>.*
-        ++call;
+        const int call = ++merge_call_no();   // one set of lines per call: merge<call>.*
         std::fprintf(stderr,
                      "hga-timing merge%d.groups %.2f\nhga-timing merge%d.members %.2f\nhga-timing merge%d.union %.2f\n"
                      "hga-timing merge%d.pairs %.2f\nhga-timing merge%d.kci_update %.2f\n",
@@ -1203,6 +1278,9 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
         core_ids = component_ids(min_size);
     }
     print_components(core_ids, out);   // :797
+    if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1")
+        std::fprintf(stderr, "hga-timing conn.device_calls %llu\nhga-timing conn.host_calls %llu\n",
+                     (unsigned long long)conn_dev_calls_, (unsigned long long)conn_host_calls_);
     return core_ids;
 }
 

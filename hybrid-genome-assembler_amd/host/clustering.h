@@ -5,8 +5,14 @@
 // The engine starts from the state construct_indices leaves (one component per read with >= 1
 // SDK hit; kmer_component_index; read metadata), which the GPU lookup produced.  The all-reads
 // connection pass (get_all_connections / the filtered get_connections call at :750-755) runs on
-// the GPU (hga_connections_run) on the device-resident indices; every later get_connections
-// call works on merged components and the edited kmer_component_index and runs on the host.
+// the GPU (hga_connections_run) on the device-resident indices.  With a device ctx the later
+// get_connections calls, on merged components and the edited kmer_component_index, run there too:
+// merge_components keeps the members, KmerID unions and categories of the components on the host
+// (the tail stage needs them) and hands the call's groups to hga_components_merge, which edits the
+// device's copy of kmer_component_index; get_connections then calls hga_components_connections.  The
+// engine builds no host kmer_component_index in that mode (kmer_component_index() fetches it on
+// demand).  HGA_HOST_CONNECTIONS=1 in the environment, or an engine without a ctx, keeps the host
+// index and runs those calls on the host.
 // The spanning-tree edge overlaps of the tail stage (approximate_read_overlap, :491-513) run on the
 // GPU too (hga_read_overlaps), in one batch over all trees, for the edges whose two endpoints were
 // never merged into: those components' KmerID lists are still the reads' own, which is what the
@@ -83,7 +89,8 @@ class ClusteringEngine {
    public:
     // State after construct_indices (ReadClusteringEngine.cpp:234-299) from the lookup's CSR
     // outputs (hga_lookup_result): read i has ReadID first_read_id + i.  `gpu` (may be null)
-    // holds the same lookup on the device for the first connection pass.
+    // holds the same lookup on the device for the first connection pass and, unless
+    // HGA_HOST_CONNECTIONS=1, the component state after merges; kci_ptr / kci_read are not read then.
     ClusteringEngine(const ClusteringConfig& cfg, bool debug, const RecordSet& reads, uint32_t first_read_id,
                      std::vector<uint64_t> hit_ptr, std::vector<uint32_t> sorted_kid, std::vector<uint64_t> first_ptr,
                      std::vector<uint32_t> first_kid, std::vector<uint32_t> first_pos,
@@ -118,7 +125,11 @@ class ClusteringEngine {
         std::set<int32_t> categories;
     };
     const std::map<ComponentID, Component>& components() const { return index_; }
-    const std::vector<std::vector<ComponentID>>& kmer_component_index() const { return kci_; }
+    // (with the component state on the device: fetched with hga_components_fetch_index on every call)
+    const std::vector<std::vector<ComponentID>>& kmer_component_index() const;
+    // get_connections calls after the first merge answered by the device / by the host
+    uint64_t connection_calls_device() const { return conn_dev_calls_; }
+    uint64_t connection_calls_host() const { return conn_host_calls_; }
     bool used_gpu() const { return gpu_calls_ > 0; }
     // Spanning-tree edges of the tail stage whose overlap came from the batch (device or hook) / from
     // the host's approximate_read_overlap.
@@ -160,8 +171,11 @@ class ClusteringEngine {
     std::vector<uint64_t> hit_ptr_, first_ptr_;
     std::vector<uint32_t> first_kid_, first_pos_;
     std::map<ComponentID, Component> index_;
-    std::vector<std::vector<ComponentID>> kci_;
+    mutable std::vector<std::vector<ComponentID>> kci_;
+    size_t n_sdk_ = 0;          // KmerIDs (kci_.size() when the host holds the index)
     hga_ctx* gpu_;
+    bool dev_comp_ = false;     // merges and post-merge connections on gpu_ (hga_components_*)
+    uint64_t conn_dev_calls_ = 0, conn_host_calls_ = 0;
     DeviceConnections dev_conn_;
     DeviceOverlaps dev_ov_;
     uint64_t ov_edges_dev_ = 0, ov_edges_host_ = 0;

@@ -339,6 +339,57 @@ hga_status hga_read_overlaps(hga_ctx* ctx, const uint32_t* x, const uint32_t* y,
                              int32_t* overlap /* n, may be NULL */, uint32_t* shared /* n, may be NULL */);
 
 /* ------------------------------------------------------------------------------
+ * Merged components — ReadClusteringEngine::merge_components
+ * (src/clustering/ReadClusteringEngine.cpp:341-422) and get_connections (:301-333) on the state
+ * merges leave.  The component view is created lazily from the ctx's current lookup result (the
+ * rank's own reads, or the whole input's index after hga_lookup_gather) and dropped by
+ * hga_lookup_load / _set_reads / _run / _gather.  hga_lookup_fetch, hga_connections_run and
+ * hga_read_overlaps keep answering for the lookup's own state, before and after merges.
+ * An id is a ReadID with at least one hit.  Its current KmerID list is the union it received as
+ * the survivor of an earlier merge, else the read's own sorted_kid slice (with duplicates).
+ * All calls are synchronous; HGA_ERR_STATE before hga_lookup_run.
+ * ------------------------------------------------------------------------------ */
+
+/* One merge_components call (:341-422).  groups: n_groups lists, ids[group_ptr[g] .. group_ptr[g+1]);
+ * the first id of a list survives (:364).  Empty and one-member lists are no-ops (:358-363).
+ * For every longer list the survivor's current list becomes the sorted distinct union of the members'
+ * lists (accumulate_kmer_ids, :340-346, :376).  Then kmer_component_index is edited (:389-414): the removal
+ * pairs are one (KmerID, member) per entry of every non-survivor member's list and one per KmerID of the
+ * union for the survivor; per KmerID the sorted removals are run against the list with the reference's
+ * two-pointer loop, which stops once the removals are exhausted (:400-412) and re-inserts nobody.
+ * HGA_ERR_INVALID, with nothing launched and no state changed: an id outside
+ * [first_read_id, first_read_id + n_reads), an id without hits in a list of two or more, an id listed
+ * twice in the call.  n_groups == 0 is HGA_OK. */
+hga_status hga_components_merge(hga_ctx* ctx, const uint64_t* group_ptr, const uint32_t* ids, uint64_t n_groups);
+
+/* get_connections (:301-333) on the current state: score(p, c) = sum over the entries of p's current
+ * list (with duplicates) of the occurrences of c in that KmerID's current index list (:311-315); c == p
+ * is dropped (:316), pairs with score >= min_score are kept (:318-325).  The result is read through
+ * hga_connections_fetch / _fetch_range in their order (score descending, then pivot, then candidate),
+ * is_good = 0.  A pivot without hits yields nothing; a pivot outside the lookup's reads is
+ * HGA_ERR_INVALID; n_pivots == 0 is HGA_OK; min_score above 32 bits yields nothing, as in
+ * hga_connections_run.  Before any merge the result equals hga_connections_run(pivots, 1, min_score, NULL). */
+hga_status hga_components_connections(hga_ctx* ctx, const uint32_t* pivots, uint64_t n_pivots,
+                                      uint64_t min_score, uint64_t* n);
+
+typedef struct hga_components_sizes {
+    uint64_t index_entries;   /* entries of the current kmer_component_index                     */
+    uint64_t survivors;       /* ids whose list is a union (survived a merge of two or more)     */
+    uint64_t survivor_kmers;  /* the summed length of their current lists                        */
+    uint64_t merges;          /* lists of two or more merged so far                              */
+} hga_components_sizes;
+hga_status hga_components_get_sizes(hga_ctx* ctx, hga_components_sizes* out);
+
+/* The current kmer_component_index (:389-414 applied so far) as a CSR of ReadIDs: ptr[K+1],
+ * ids[index_entries]; either may be NULL. */
+hga_status hga_components_fetch_index(hga_ctx* ctx, uint64_t* ptr, uint32_t* ids);
+/* The current KmerID list of one id (ReadComponent::discriminative_kmer_ids, :376): *n is always
+ * set; kmers (may be NULL) receives *n entries. */
+hga_status hga_components_fetch_kmers(hga_ctx* ctx, uint32_t id, uint32_t* kmers, uint64_t* n);
+/* Back to the lookup's state (what construct_indices leaves, :234-299). */
+hga_status hga_components_reset(hga_ctx* ctx);
+
+/* ------------------------------------------------------------------------------
  * Measurement: per-kernel device time, recorded with HIP events on the ctx stream.
  * ------------------------------------------------------------------------------ */
 hga_status hga_profile_enable(hga_ctx* ctx, int on);
