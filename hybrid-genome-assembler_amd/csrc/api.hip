@@ -158,6 +158,17 @@ hga_status hga_components_connections(hga_ctx* c, const uint32_t* pivots, uint64
     });
 }
 
+hga_status hga_components_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap,
+                                   uint32_t* shared) {
+    HGA_CTX_GUARD(c, hga::components_overlaps(c, x, y, n, overlap, shared));
+}
+
+hga_status hga_components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
+                                     const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
+                                     uint64_t* set_size) {
+    HGA_CTX_GUARD(c, hga::components_set_scores(c, set_ptr, ids, n_sets, pair_a, pair_b, n_pairs, score, set_size));
+}
+
 hga_status hga_components_get_sizes(hga_ctx* c, hga_components_sizes* out) {
     HGA_CTX_GUARD(c, {
         HGA_REQUIRE(out, HGA_ERR_INVALID, "null out pointer");

@@ -25,8 +25,22 @@
 // n_reads wide, in HBM.  cc_pairs counts, then emits (pivot, candidate, score) with score >= min_score
 // into the ctx's connection buffers; connections_order (connect.hip) sorts and decodes them.
 //
+// Overlaps on the current lists (hga_components_overlaps: approximate_read_overlap :491-507 with merge
+// survivors).  co_wave, one wave per pair in ov_wave's shape (overlap.hip): the shared KmerIDs are those of
+// the two current lists, their positions each id's own read's (first_kid / first_pos), 0 when absent.
+//
+// Set scores (hga_components_set_scores: accumulate_kmer_ids :341-347 and the tail intersections
+// :621-624).  Bitmaps, not sorted merges: a row of one bit per KmerID per set in HBM.  cs_bounds cuts every
+// member list at the KmerID tile borders, cs_mark ORs a tile's share of every member list into its set's
+// row (1024 entries per workgroup, so a union of most of K spreads over many), cs_pairs takes
+// popcount(row a & row b) with 16-byte loads, one workgroup per pair; the sizes are the pairs (s, s).  The
+// rows of one tile stay within CS_ROW_BYTES (HGA_SETS_BYTES); the host adds the tiles' counts up.
+//
 // Every loop runs over static wave or workgroup strides with wave-uniform bounds; no kernel draws work
 // from a device counter.
+#include <climits>
+#include <cstdlib>
+
 #include "hga_internal.hpp"
 
 namespace hga {
@@ -34,6 +48,10 @@ namespace {
 
 constexpr uint64_t CC_ROW_BYTES = 256ull << 20;   // score rows of one batch of pivots
 constexpr int CC_T = 256;                         // cc_accum: list entries per workgroup
+constexpr uint64_t CO_CHUNK = 1ull << 22;         // co_wave: pairs per launch (16 MiB per scratch array)
+constexpr uint64_t CS_ROW_BYTES = 256ull << 20;   // set scores: the bitmap rows of one KmerID tile (HGA_SETS_BYTES)
+constexpr int CS_E = 1024;                        // cs_mark: list entries per workgroup
+constexpr uint64_t CS_CHUNK = 1ull << 22;         // cs_pairs: pairs per launch
 
 inline unsigned cm_blocks(uint64_t n, uint64_t t, uint64_t cap) {
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + t - 1) / t, cap));
@@ -292,6 +310,162 @@ __global__ void __launch_bounds__(256) cc_pairs(const uint32_t* __restrict__ row
                 os[o] = s;
             }
         }
+    }
+}
+
+// kmer_positions[kid] of read r: the position in its own first_kid slice, 0 when the read lacks the KmerID
+__device__ __forceinline__ int co_pos(const uint64_t* __restrict__ fptr, const uint32_t* __restrict__ fkid,
+                                      const uint32_t* __restrict__ fpos, uint32_t r, uint32_t kid) {
+    uint64_t lo = fptr[r], hi = fptr[r + 1];
+    const uint64_t end = hi;
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (fkid[mid] < kid) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && fkid[lo] == kid ? (int)fpos[lo] : 0;
+}
+
+// One wave per pair, as ov_wave (overlap.hip): the lanes stride over the shorter current list, skip an
+// entry equal to its predecessor and binary-search the longer list.  A pair of ids without an override
+// takes the two first_kid lists (distinct, their positions beside them); any other pair looks each
+// shared KmerID up in either read's own first_kid slice.
+__global__ __launch_bounds__(256) void co_wave(CmLists v, const uint64_t* __restrict__ fptr,
+                                               const uint32_t* __restrict__ fkid, const uint32_t* __restrict__ fpos,
+                                               const uint32_t* __restrict__ ex, const uint32_t* __restrict__ ey,
+                                               uint32_t n, uint32_t first_id, int32_t* __restrict__ ov,
+                                               uint32_t* __restrict__ sh) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    const uint32_t waves = gridDim.x * 4u;
+    for (uint32_t e = wave; e < n; e += waves) {
+        uint32_t ra = ex[e] - first_id, rb = ey[e] - first_id;   // validated on the host
+        const bool plain = v.ovr_off[ra] == ~0ull && v.ovr_off[rb] == ~0ull;   // the same in every lane
+        const uint32_t *A, *B;
+        uint32_t la, lb;
+        if (plain) {
+            A = fkid + fptr[ra];
+            la = (uint32_t)(fptr[ra + 1] - fptr[ra]);
+            B = fkid + fptr[rb];
+            lb = (uint32_t)(fptr[rb + 1] - fptr[rb]);
+        } else {
+            A = cm_list(v, ra, la);
+            B = cm_list(v, rb, lb);
+        }
+        if (la > lb) {   // a: the shorter list; pa / pb below follow the swap, the result is symmetric
+            const uint32_t* tp = A;
+            A = B;
+            B = tp;
+            const uint32_t tl = la;
+            la = lb;
+            lb = tl;
+            const uint32_t tr = ra;
+            ra = rb;
+            rb = tr;
+        }
+        const uint64_t a0 = fptr[ra], b0 = fptr[rb];
+        int cnt = 0, min_a = INT_MAX, max_a = INT_MIN, min_b = INT_MAX, max_b = INT_MIN;
+        uint32_t lo = 0;   // a lane's KmerIDs do not descend: each search starts where its last one ended
+        for (uint32_t i = (uint32_t)lane; i < la; i += 64u) {
+            const uint32_t kid = A[i];
+            if (i > 0 && A[i - 1] == kid) continue;
+            uint32_t hi = lb;
+            while (lo < hi) {   // lower_bound(B, kid)
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (B[mid] < kid) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < lb && B[lo] == kid) {
+                const int pa = plain ? (int)fpos[a0 + i] : co_pos(fptr, fkid, fpos, ra, kid);
+                const int pb = plain ? (int)fpos[b0 + lo] : co_pos(fptr, fkid, fpos, rb, kid);
+                ++cnt;
+                min_a = min(min_a, pa);
+                max_a = max(max_a, pa);
+                min_b = min(min_b, pb);
+                max_b = max(max_b, pb);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            cnt += __shfl_xor(cnt, o, 64);
+            min_a = min(min_a, __shfl_xor(min_a, o, 64));
+            max_a = max(max_a, __shfl_xor(max_a, o, 64));
+            min_b = min(min_b, __shfl_xor(min_b, o, 64));
+            max_b = max(max_b, __shfl_xor(max_b, o, 64));
+        }
+        if (lane == 0) {
+            ov[e] = cnt ? max(max_a - min_a, max_b - min_b) : 0;
+            sh[e] = (uint32_t)cnt;
+        }
+    }
+}
+
+// Set scores.  Member m of the call: read mread[m] in set mset[m].  bnd[m * (T + 1) + t]: the first entry
+// of the member's current (ascending) list with KmerID >= t * tile_k, so tile t's share of the list is
+// [bnd[.. + t], bnd[.. + t + 1]).
+__global__ void __launch_bounds__(256) cs_bounds(CmLists v, const uint32_t* __restrict__ mread, uint32_t M, uint32_t T1,
+                                                 uint64_t tile_k, uint32_t* __restrict__ bnd) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (uint64_t)M * T1) return;
+    const uint32_t m = (uint32_t)(j / T1), t = (uint32_t)(j % T1);
+    uint32_t n;
+    const uint32_t* l = cm_list(v, mread[m], n);
+    const uint64_t want = (uint64_t)t * tile_k;
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((uint64_t)l[mid] < want) lo = mid + 1;
+        else hi = mid;
+    }
+    bnd[j] = lo;
+}
+
+// Work item w: entries [wstart[w], wstart[w] + CS_E) of tile t's share of member wmem[w]'s list, each
+// ORed as a bit into the member's set row (roww words wide, bit 0 = KmerID k0).  The work items cover a
+// member's whole list; those past the tile's share do nothing.
+__global__ void __launch_bounds__(256) cs_mark(CmLists v, const uint32_t* __restrict__ mread,
+                                               const uint32_t* __restrict__ mset, const uint32_t* __restrict__ wmem,
+                                               const uint32_t* __restrict__ wstart, uint32_t W,
+                                               const uint32_t* __restrict__ bnd, uint32_t T1, uint32_t t, uint32_t k0,
+                                               uint64_t roww, uint32_t* __restrict__ rows) {
+    for (uint32_t w = blockIdx.x; w < W; w += gridDim.x) {
+        const uint32_t m = wmem[w];
+        const uint64_t lo = bnd[(uint64_t)m * T1 + t], hi = bnd[(uint64_t)m * T1 + t + 1];
+        uint32_t n;
+        const uint32_t* l = cm_list(v, mread[m], n);
+        uint32_t* __restrict__ row = rows + (uint64_t)mset[m] * roww;
+        const uint64_t s = lo + wstart[w];
+#pragma unroll
+        for (uint32_t j = 0; j < (uint32_t)CS_E; j += 256u) {
+            const uint64_t e = s + j + threadIdx.x;
+            if (e < hi) {
+                const uint32_t d = l[e] - k0;
+                atomicOr(&row[d >> 5], 1u << (d & 31u));
+            }
+        }
+    }
+}
+
+// One workgroup per pair: popcount(row a & row b), rows of row4 16-byte words.
+__global__ void __launch_bounds__(256) cs_pairs(const uint4* __restrict__ rows, uint64_t row4,
+                                                const uint32_t* __restrict__ pa, const uint32_t* __restrict__ pb,
+                                                uint32_t n, unsigned long long* __restrict__ out) {
+    __shared__ uint32_t ws[4];
+    const uint32_t t = threadIdx.x, lane = t & 63u;
+    for (uint32_t p = blockIdx.x; p < n; p += gridDim.x) {
+        const uint4* __restrict__ A = rows + (uint64_t)pa[p] * row4;
+        const uint4* __restrict__ B = rows + (uint64_t)pb[p] * row4;
+        uint32_t c = 0;   // a row holds fewer than 2^32 bits
+        for (uint64_t i = t; i < row4; i += 256u) {
+            const uint4 a = A[i], b = B[i];
+            c += (uint32_t)(__popc(a.x & b.x) + __popc(a.y & b.y) + __popc(a.z & b.z) + __popc(a.w & b.w));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) ws[t >> 6] = c;
+        __syncthreads();
+        if (t == 0) out[p] = (unsigned long long)ws[0] + ws[1] + ws[2] + ws[3];
+        __syncthreads();   // ws is reused by the next pair
     }
 }
 
@@ -591,6 +765,169 @@ void components_connections(hga_ctx* c, const uint32_t* pivots, uint64_t n_piv, 
     }
     connections_order(c, n, mxs, ms);
     *n_out = n;
+}
+
+void components_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap,
+                         uint32_t* shared) {
+    auto& L = c->lookup;
+    auto& S = c->overlap;
+    HGA_REQUIRE(L.ran, HGA_ERR_STATE, "hga_lookup_run not called");
+    if (n == 0) return;
+    HGA_REQUIRE(x && y, HGA_ERR_INVALID, "null id list with n > 0");
+    const uint64_t first = L.first_read_id, nr = L.n_reads;
+    for (uint64_t i = 0; i < n; ++i)   // before anything is launched
+        HGA_REQUIRE(x[i] >= first && x[i] - first < nr && y[i] >= first && y[i] - first < nr, HGA_ERR_INVALID,
+                    "id outside the lookup's reads");
+    ensure_view(c);
+    if (L.hits == 0) {   // no read has a hit: every list is empty
+        if (overlap) std::memset(overlap, 0, n * sizeof(int32_t));
+        if (shared) std::memset(shared, 0, n * sizeof(uint32_t));
+        return;
+    }
+    const uint64_t cap = std::min(n, CO_CHUNK);
+    uint32_t* dx = static_cast<uint32_t*>(S.x.ensure(cap * 4));
+    uint32_t* dy = static_cast<uint32_t*>(S.y.ensure(cap * 4));
+    int32_t* dov = static_cast<int32_t*>(S.ov.ensure(cap * 4));
+    uint32_t* dsh = static_cast<uint32_t*>(S.sh.ensure(cap * 4));
+    const CmLists lists = lists_of(c);
+    for (uint64_t at = 0; at < n; at += CO_CHUNK) {
+        const uint64_t m = std::min(CO_CHUNK, n - at);
+        HGA_HIP(hipMemcpyAsync(dx, x + at, m * 4, hipMemcpyHostToDevice, c->stream));
+        HGA_HIP(hipMemcpyAsync(dy, y + at, m * 4, hipMemcpyHostToDevice, c->stream));
+        const unsigned grid = (unsigned)std::min<uint64_t>((m + 3) / 4, (uint64_t)c->num_cu * 8);
+        c->launch("co_wave", [&] {
+            hipLaunchKernelGGL(co_wave, dim3(grid), dim3(256), 0, c->stream, lists, L.first_ptr.as<uint64_t>(),
+                               L.first_kid.as<uint32_t>(), L.first_pos.as<uint32_t>(), dx, dy, (uint32_t)m,
+                               L.first_read_id, dov, dsh);
+        });
+        c->check_launch("co_wave");
+        if (overlap) HGA_HIP(hipMemcpyAsync(overlap + at, dov, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (shared) HGA_HIP(hipMemcpyAsync(shared + at, dsh, m * 4, hipMemcpyDeviceToHost, c->stream));
+        c->sync();   // the scratch is reused by the next chunk
+    }
+}
+
+// One bitmap row per set, a bit per KmerID.  When n_sets rows of all K bits exceed the byte budget the
+// call runs over KmerID tiles of tile_k ids: each tile marks its share of every member list, the pair
+// kernel counts it, and the host adds the tiles' counts up.  A row is never narrower than one 16-byte
+// word, so more than budget / 16 sets exceed the budget by that much.
+void components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
+                           const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
+                           uint64_t* set_size) {
+    auto& L = c->lookup;
+    auto& V = c->comp;
+    HGA_REQUIRE(L.ran, HGA_ERR_STATE, "hga_lookup_run not called");
+    if (n_sets == 0) {
+        HGA_REQUIRE(n_pairs == 0, HGA_ERR_INVALID, "pair index outside the sets");
+        return;
+    }
+    HGA_REQUIRE(set_ptr, HGA_ERR_INVALID, "null set_ptr with n_sets > 0");
+    HGA_REQUIRE(n_pairs == 0 || (pair_a && pair_b && score), HGA_ERR_INVALID, "null pair list or score with n_pairs > 0");
+    HGA_REQUIRE(n_sets < 0xFFFFFFFFull, HGA_ERR_INVALID, "too many sets");
+    for (uint64_t s = 0; s < n_sets; ++s)
+        HGA_REQUIRE(set_ptr[s + 1] >= set_ptr[s], HGA_ERR_INVALID, "set_ptr must be non-decreasing");
+    HGA_REQUIRE(ids || set_ptr[n_sets] == set_ptr[0], HGA_ERR_INVALID, "null ids");
+    const uint64_t first = L.first_read_id, nr = L.n_reads;
+    for (uint64_t i = set_ptr[0]; i < set_ptr[n_sets]; ++i)
+        HGA_REQUIRE(ids[i] >= first && ids[i] - first < nr, HGA_ERR_INVALID, "id outside the lookup's reads");
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        HGA_REQUIRE(pair_a[p] < n_sets && pair_b[p] < n_sets, HGA_ERR_INVALID, "pair index outside the sets");
+    ensure_view(c);
+    // the pairs asked for, then (s, s) per set for the sizes
+    const uint64_t P = n_pairs + (set_size ? n_sets : 0);
+    if (n_pairs) std::memset(score, 0, n_pairs * 8);
+    if (set_size) std::memset(set_size, 0, n_sets * 8);
+    const uint64_t K = L.n_sdk;
+    if (P == 0 || K == 0 || L.hits == 0) return;
+    // members with a non-empty current list, and their lists cut into work items of CS_E entries
+    std::vector<uint32_t> mread, mset, wmem, wstart;
+    for (uint64_t s = 0; s < n_sets; ++s)
+        for (uint64_t i = set_ptr[s]; i < set_ptr[s + 1]; ++i) {
+            const uint32_t r = (uint32_t)(ids[i] - first);
+            const uint32_t ln = cur_len(V, r);
+            if (!ln) continue;
+            HGA_REQUIRE(mread.size() < 0xFFFFFFFFull, HGA_ERR_OOM, "too many set members");
+            const uint32_t m = (uint32_t)mread.size();
+            mread.push_back(r);
+            mset.push_back((uint32_t)s);
+            for (uint32_t at = 0; at < ln; at += CS_E) {
+                wmem.push_back(m);
+                wstart.push_back(at);
+                if (ln - at <= (uint32_t)CS_E) break;   // no wrap for lists near 2^32
+            }
+        }
+    const uint64_t M = mread.size(), W = wmem.size();
+    HGA_REQUIRE(W < (1ull << 32), HGA_ERR_OOM, "too many list entries for one set-score call");
+    uint64_t budget = CS_ROW_BYTES;
+    if (const char* e = std::getenv("HGA_SETS_BYTES")) {
+        char* end = nullptr;
+        const unsigned long long b = std::strtoull(e, &end, 10);
+        if (end != e && b > 0) budget = b;
+    }
+    const uint64_t full4 = (K + 127) / 128;   // 16-byte words of a row that holds every KmerID
+    const uint64_t row4 = std::min(full4, std::max<uint64_t>(1, budget / 16 / n_sets));
+    const uint64_t tile_k = row4 * 128, roww = row4 * 4;
+    const uint64_t T = (K + tile_k - 1) / tile_k;
+    HGA_REQUIRE(M * (T + 1) < (1ull << 32), HGA_ERR_OOM, "too many KmerID tiles for one set-score call");
+    uint32_t* rows = static_cast<uint32_t*>(V.rows.ensure(n_sets * row4 * 16));
+    const uint64_t pcap = std::min(P, CS_CHUNK);
+    // uploads: mread | mset | wmem | wstart | bnd (u32), then the pairs and scores of one chunk
+    uint32_t* d_mread = static_cast<uint32_t*>(V.work.ensure(std::max<uint64_t>(1, 2 * M + 2 * W + M * (T + 1)) * 4));
+    uint32_t* d_mset = d_mread + M;
+    uint32_t* d_wmem = d_mset + M;
+    uint32_t* d_wstart = d_wmem + W;
+    uint32_t* d_bnd = d_wstart + W;
+    char* mem = static_cast<char*>(V.mem.ensure(pcap * 16));
+    auto* d_out = reinterpret_cast<unsigned long long*>(mem);
+    uint32_t* d_pa = reinterpret_cast<uint32_t*>(mem + pcap * 8);
+    uint32_t* d_pb = d_pa + pcap;
+    const CmLists lists = lists_of(c);
+    if (M) {
+        HGA_HIP(hipMemcpyAsync(d_mread, mread.data(), M * 4, hipMemcpyHostToDevice, c->stream));
+        HGA_HIP(hipMemcpyAsync(d_mset, mset.data(), M * 4, hipMemcpyHostToDevice, c->stream));
+        HGA_HIP(hipMemcpyAsync(d_wmem, wmem.data(), W * 4, hipMemcpyHostToDevice, c->stream));
+        HGA_HIP(hipMemcpyAsync(d_wstart, wstart.data(), W * 4, hipMemcpyHostToDevice, c->stream));
+        c->launch("cs_bounds", [&] {
+            hipLaunchKernelGGL(cs_bounds, dim3((unsigned)((M * (T + 1) + 255) / 256)), dim3(256), 0, c->stream, lists,
+                               d_mread, (uint32_t)M, (uint32_t)(T + 1), tile_k, d_bnd);
+        });
+        c->check_launch("cs_bounds");
+    }
+    std::vector<uint32_t> ha(pcap), hb(pcap);
+    std::vector<unsigned long long> got(pcap);
+    for (uint64_t t = 0; t < T; ++t) {
+        HGA_HIP(hipMemsetAsync(rows, 0, n_sets * row4 * 16, c->stream));
+        if (M) {
+            c->launch("cs_mark", [&] {
+                hipLaunchKernelGGL(cs_mark, dim3(cm_blocks(W, 1, (uint64_t)c->num_cu * 8)), dim3(256), 0, c->stream, lists,
+                                   d_mread, d_mset, d_wmem, d_wstart, (uint32_t)W, d_bnd, (uint32_t)(T + 1), (uint32_t)t,
+                                   (uint32_t)(t * tile_k), roww, rows);
+            });
+            c->check_launch("cs_mark");
+        }
+        for (uint64_t at = 0; at < P; at += CS_CHUNK) {
+            const uint64_t m = std::min(CS_CHUNK, P - at);
+            for (uint64_t i = 0; i < m; ++i) {
+                const uint64_t p = at + i;
+                ha[i] = p < n_pairs ? pair_a[p] : (uint32_t)(p - n_pairs);
+                hb[i] = p < n_pairs ? pair_b[p] : (uint32_t)(p - n_pairs);
+            }
+            HGA_HIP(hipMemcpyAsync(d_pa, ha.data(), m * 4, hipMemcpyHostToDevice, c->stream));
+            HGA_HIP(hipMemcpyAsync(d_pb, hb.data(), m * 4, hipMemcpyHostToDevice, c->stream));
+            c->launch("cs_pairs", [&] {
+                hipLaunchKernelGGL(cs_pairs, dim3(cm_blocks(m, 1, (uint64_t)c->num_cu * 8)), dim3(256), 0, c->stream,
+                                   reinterpret_cast<const uint4*>(rows), row4, d_pa, d_pb, (uint32_t)m, d_out);
+            });
+            c->check_launch("cs_pairs");
+            HGA_HIP(hipMemcpyAsync(got.data(), d_out, m * 8, hipMemcpyDeviceToHost, c->stream));
+            c->sync();   // the staged pairs are reused by the next chunk
+            for (uint64_t i = 0; i < m; ++i) {
+                const uint64_t p = at + i;
+                if (p < n_pairs) score[p] += got[i];
+                else set_size[p - n_pairs] += got[i];
+            }
+        }
+    }
 }
 
 void components_sizes(hga_ctx* c, hga_components_sizes* out) {

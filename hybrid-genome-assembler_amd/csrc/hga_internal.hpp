@@ -356,6 +356,10 @@ void connections_order(hga_ctx* c, uint64_t n, uint32_t mxs, uint32_t ms);
 void components_drop(hga_ctx* c);
 void components_merge(hga_ctx* c, const uint64_t* group_ptr, const uint32_t* ids, uint64_t n_groups);
 void components_connections(hga_ctx* c, const uint32_t* pivots, uint64_t n_piv, uint64_t min_score, uint64_t* n_out);
+void components_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap, uint32_t* shared);
+void components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
+                           const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
+                           uint64_t* set_size);
 void components_sizes(hga_ctx* c, hga_components_sizes* out);
 void components_fetch_index(hga_ctx* c, uint64_t* ptr, uint32_t* ids);
 void components_fetch_kmers(hga_ctx* c, uint32_t id, uint32_t* kmers, uint64_t* n);

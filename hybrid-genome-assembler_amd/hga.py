@@ -99,6 +99,8 @@ HGA_SYMBOLS = {
     "hga_read_overlaps": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _i32p, _u32p]),
     "hga_components_merge": (C.c_int, [_vp, _u64p, _u32p, C.c_uint64]),
     "hga_components_connections": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint64, _u64p]),
+    "hga_components_overlaps": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _i32p, _u32p]),
+    "hga_components_set_scores": (C.c_int, [_vp, _u64p, _u32p, C.c_uint64, _u32p, _u32p, C.c_uint64, _u64p, _u64p]),
     "hga_components_get_sizes": (C.c_int, [_vp, C.POINTER(ComponentsSizes)]),
     "hga_components_fetch_index": (C.c_int, [_vp, _u64p, _u32p]),
     "hga_components_fetch_kmers": (C.c_int, [_vp, C.c_uint32, _u32p, _u64p]),
@@ -480,6 +482,29 @@ class Ctx:
         self._conn_n = n.value
         return n.value
 
+    def components_overlaps(self, x, y):
+        """(overlap int32[n], shared uint32[n]) of the id pairs (x[i], y[i]) on the current component lists."""
+        xv, yv = np.ascontiguousarray(x, np.uint32), np.ascontiguousarray(y, np.uint32)
+        if xv.shape != yv.shape or xv.ndim != 1:
+            raise ValueError("x and y must be one-dimensional and of equal length")
+        ov, sh = np.zeros(len(xv), np.int32), np.zeros(len(xv), np.uint32)
+        _ck(lib().hga_components_overlaps(self._h, _p(xv, C.c_uint32), _p(yv, C.c_uint32), len(xv), _p(ov, C.c_int32),
+                                          _p(sh, C.c_uint32)))
+        return ov, sh
+
+    def components_set_scores(self, sets, pairs):
+        """sets: a list of id lists, pairs: (n, 2) set indices.  (score uint64[n_pairs], set_size
+        uint64[n_sets]): the sizes of the pairwise intersections of the sets' KmerID unions, and of the unions."""
+        sp = np.zeros(len(sets) + 1, np.uint64)
+        sp[1:] = np.cumsum([len(s) for s in sets], dtype=np.uint64)
+        ids = np.ascontiguousarray([i for s in sets for i in s], np.uint32)
+        pr = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        pa, pb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        score, size = np.zeros(len(pr), np.uint64), np.zeros(len(sets), np.uint64)
+        _ck(lib().hga_components_set_scores(self._h, _p(sp, C.c_uint64), _p(ids, C.c_uint32), len(sets), _p(pa, C.c_uint32),
+                                            _p(pb, C.c_uint32), len(pr), _p(score, C.c_uint64), _p(size, C.c_uint64)))
+        return score, size
+
     def components_sizes(self) -> ComponentsSizes:
         s = ComponentsSizes()
         _ck(lib().hga_components_get_sizes(self._h, C.byref(s)))
@@ -773,13 +798,16 @@ def sym_eigen(a):
 
 
 def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None, debug=False, first_read_id=1,
-                 start=None, end=None, batched_overlaps=False, stats=None):
+                 start=None, end=None, batched_overlaps=False, stats=None, device_sets=False):
     """run_clustering after construct_indices on the host (no device state): (component ids,
     per-read component id (0 = none), log text).  start / end: the reads' simulator coordinates
     (print_components' intervals under debug), None = 0.
     batched_overlaps: the tail stage takes its spanning-tree edge overlaps through the batched hook
     (the device path's batching and eligibility rule) with hga_read_overlaps' semantics computed on
-    the host.  stats: a dict that receives "overlap_edges_batched" and "overlap_edges_host"."""
+    the host.  stats: a dict that receives "overlap_edges_batched" and "overlap_edges_host".
+    device_sets: the tail stage runs the batching of HGA_DEVICE_SETS=1 (every spanning-tree edge in one
+    component-overlap call, one set-score call over the tail ids still in the index) through hooks bound
+    to the engine's host implementations."""
     L = cluster_lib()
     cfg = cfg or cluster_config()
     off = np.ascontiguousarray(offsets, np.uint64)
@@ -799,7 +827,8 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
                                _p(a["hit_ptr"], C.c_uint64), _p(a["sorted_kid"], C.c_uint32), _p(a["first_ptr"], C.c_uint64),
                                _p(a["first_kid"], C.c_uint32), _p(a["first_pos"], C.c_uint32), _p(a["kci_ptr"], C.c_uint64),
                                _p(a["kci_read"], C.c_uint32), len(a["kci_ptr"]) - 1, C.byref(cfg), 1 if debug else 0,
-                               C.byref(ip), C.byref(ni), C.byref(op), C.byref(lp), 1 if batched_overlaps else 0,
+                               C.byref(ip), C.byref(ni), C.byref(op), C.byref(lp),
+                               (1 if batched_overlaps else 0) | (2 if device_sets else 0),
                                _p(ove, C.c_uint64)))
     if stats is not None:
         stats["overlap_edges_batched"], stats["overlap_edges_host"] = int(ove[0]), int(ove[1])

@@ -149,10 +149,16 @@ int main(int argc, char* argv[]) {
     hga_lookup_sizes sz;
     check(hga_lookup_get_sizes(ctx, &sz), "hga_lookup_get_sizes");
     std::vector<uint64_t> hit_ptr(sz.n_reads + 1), first_ptr(sz.n_reads + 1), kci_ptr;
-    std::vector<uint32_t> sorted_kid(sz.hits), first_kid(sz.firsts), first_pos(sz.firsts), kci_read;
+    std::vector<uint32_t> sorted_kid, first_kid(sz.firsts), first_pos(sz.firsts), kci_read;
     hga_lookup_result res{};
     res.hit_ptr = hit_ptr.data();
-    res.sorted_kid = sorted_kid.data();
+    // HGA_DEVICE_SETS=1: the engine reads no KmerID list on the host, so sorted_kid stays on the device
+    // (--index-out below reads it back itself)
+    bool have_skid = !hgah::ClusteringEngine::device_sets_requested();
+    if (have_skid) {
+        sorted_kid.resize(sz.hits);
+        res.sorted_kid = sorted_kid.data();
+    }
     res.first_ptr = first_ptr.data();
     res.first_kid = first_kid.data();
     res.first_pos = first_pos.data();
@@ -202,6 +208,13 @@ int main(int argc, char* argv[]) {
         std::FILE* f = std::fopen(index_out.c_str(), "wb");
         if (!f) throw std::runtime_error("cannot write " + index_out);
         need_kci();
+        if (!have_skid) {
+            sorted_kid.resize(sz.hits);
+            hga_lookup_result r3{};
+            r3.sorted_kid = sorted_kid.data();
+            check(hga_lookup_fetch(ctx, &r3), "hga_lookup_fetch");
+            have_skid = true;
+        }
         const uint64_t hdr[5] = {sz.n_reads, sz.hits, sz.firsts, sz.n_sdk, (uint64_t)k};
         std::fwrite(hdr, 8, 5, f);
         std::fwrite(hit_ptr.data(), 8, hit_ptr.size(), f);

@@ -73,7 +73,10 @@ void hgc_free(void* p) { std::free(p); }
 // hgc_cluster_batched: the same with the tail stage's batched overlap hook (set_device_overlaps) set
 // to the engine's host implementation of hga_read_overlaps when batched != 0 — the device path's
 // batching and eligibility rule without a device; ov_edges[2] (may be null) receives the tail stage's
-// edge counts {from the batch, from the host's approximate_read_overlap}.
+// edge counts {from the batch, from the host's approximate_read_overlap}.  batched is a set of bit flags:
+// 1 is the hook above; 2 sets the component-overlap and set-score hooks (set_device_component_overlaps,
+// set_device_set_scores) to the engine's host implementations, so that the tail stage runs the batching
+// of HGA_DEVICE_SETS=1 (every edge in one call, one set-score call over ids filtered through the index).
 int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
                 const uint32_t* end, uint64_t n_reads,
                 uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
@@ -108,10 +111,18 @@ int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_
                                  std::vector<uint32_t>(first_pos, first_pos + U),
                                  std::vector<uint64_t>(kci_ptr, kci_ptr + n_sdk + 1),
                                  std::vector<uint32_t>(kci_read, kci_read + HK), nullptr);
-        if (batched)
+        if (batched & 1)
             e.set_device_overlaps([&e](const std::vector<hgah::ComponentID>& x, const std::vector<hgah::ComponentID>& y) {
                 return e.host_read_overlaps(x, y);
             });
+        if (batched & 2) {
+            e.set_device_component_overlaps([&e](const std::vector<hgah::ComponentID>& x, const std::vector<hgah::ComponentID>& y) {
+                return e.host_component_overlaps(x, y);
+            });
+            e.set_device_set_scores([&e](const std::vector<hgah::ComponentList>& sets, const hgah::ClusteringEngine::SetPairs& pairs) {
+                return e.host_set_scores(sets, pairs);
+            });
+        }
         std::ostringstream log;
         const auto ids = e.run(log);
         if (ov_edges) {

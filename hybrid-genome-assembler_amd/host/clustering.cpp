@@ -528,18 +528,21 @@ ClusteringEngine::ClusteringEngine(const ClusteringConfig& cfg, bool debug, cons
     const uint64_t n = reads.size();
     if (hit_ptr_.size() != n + 1 || first_ptr_.size() != n + 1)
         throw std::invalid_argument("index arrays do not match the reads");
+    const char* host_conn = std::getenv("HGA_HOST_CONNECTIONS");
+    dev_comp_ = gpu_ && !(host_conn && std::string(host_conn) == "1");
+    dev_sets_ = dev_comp_ && device_sets_requested();   // the KmerID lists stay on the device
+    if (!dev_sets_ && sorted_kid.size() != hit_ptr_[n]) throw std::invalid_argument("sorted_kid does not match hit_ptr");
     for (uint64_t i = 0; i < n; ++i) {   // construct_indices :256-276
         if (hit_ptr_[i + 1] == hit_ptr_[i]) continue;
         Component c;
         c.reads = {first_id_ + (uint32_t)i};
-        c.kmers.assign(sorted_kid.begin() + (int64_t)hit_ptr_[i], sorted_kid.begin() + (int64_t)hit_ptr_[i + 1]);
+        if (!dev_sets_)
+            c.kmers.assign(sorted_kid.begin() + (int64_t)hit_ptr_[i], sorted_kid.begin() + (int64_t)hit_ptr_[i + 1]);
         c.categories = {reads.category[i]};
         index_.emplace_hint(index_.end(), first_id_ + (uint32_t)i, std::move(c));
     }
     // (built serially: the same construction on the host threads measured slower, 100 -> 155 ms at C3 —
     // 1.9 M small allocations contend in the allocator)
-    const char* host_conn = std::getenv("HGA_HOST_CONNECTIONS");
-    dev_comp_ = gpu_ && !(host_conn && std::string(host_conn) == "1");
     if (dev_comp_) {   // the index stays on the device (hga_components_*)
         hga_lookup_sizes sz;
         if (hga_lookup_get_sizes(gpu_, &sz) != HGA_OK)
@@ -566,6 +569,26 @@ const std::vector<std::vector<ComponentID>>& ClusteringEngine::kmer_component_in
     for (size_t k = 0; k < n_sdk_; ++k)
         kci_[k].assign(ids.begin() + (int64_t)ptr[k], ids.begin() + (int64_t)ptr[k + 1]);
     return kci_;
+}
+
+bool ClusteringEngine::device_sets_requested() {
+    auto on = [](const char* name) {
+        const char* v = std::getenv(name);
+        return v && std::string(v) == "1";
+    };
+    return on("HGA_DEVICE_SETS") && !on("HGA_HOST_CONNECTIONS") && !on("HGA_HOST_OVERLAPS");
+}
+
+bool ClusteringEngine::sets_mode() const { return dev_sets_ || (dev_cov_ && dev_sets_fn_); }
+
+// discriminative_kmer_ids.size() of a component (the :750 filter).
+size_t ClusteringEngine::kmer_count(ComponentID id) const {
+    if (!dev_sets_) return index_.at(id).kmers.size();
+    if (pristine_) return (size_t)(hit_ptr_[id - first_id_ + 1] - hit_ptr_[id - first_id_]);
+    uint64_t n = 0;
+    if (hga_components_fetch_kmers(gpu_, id, nullptr, &n) != HGA_OK)
+        throw std::runtime_error(std::string("hga_components_fetch_kmers: ") + hga_last_error());
+    return (size_t)n;
 }
 
 uint32_t ClusteringEngine::read_length(ComponentID r) const {   // ReadMetaData::length
@@ -751,7 +774,8 @@ std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<Co
         }
         const auto q1 = clk::now();
         std::vector<KmerID> acc;
-        if (total > nk / 16 + 64) {   // accumulate_kmer_ids as a mark pass (ids < nk), both halves threaded
+        if (dev_sets_) {   // the union is hga_components_merge's alone
+        } else if (total > nk / 16 + 64) {   // accumulate_kmer_ids as a mark pass (ids < nk), both halves threaded
             if (mark.empty()) mark.assign(nk, 0);
             par(ids.size(), 64, [&](int, size_t a, size_t b) {
                 for (size_t i = a; i < b; ++i)
@@ -770,7 +794,7 @@ std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<Co
             acc = accumulate_kmer_ids(ids);
         }
         Component& survivor = index_.at(ids[0]);
-        survivor.kmers = std::move(acc);
+        if (!dev_sets_) survivor.kmers = std::move(acc);
         survivor.categories = cats;
         survivor.reads = contained;
         merged_ids.push_back(ids[0]);
@@ -805,10 +829,10 @@ std::vector<ComponentID> ClusteringEngine::merge_components(const std::vector<Co
         if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1") {
             auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             const int call = ++merge_call_no();
-            std::fprintf(stderr,
-                         "hga-timing merge%d.groups %.2f\nhga-timing merge%d.members %.2f\nhga-timing merge%d.union %.2f\n"
-                         "hga-timing merge%d.device %.2f\n",
-                         call, ms(t_start, t_groups), call, t_members, call, t_union, call, ms(t_groups, clk::now()));
+            std::fprintf(stderr, "hga-timing merge%d.groups %.2f\nhga-timing merge%d.members %.2f\n", call,
+                         ms(t_start, t_groups), call, t_members);
+            if (!dev_sets_) std::fprintf(stderr, "hga-timing merge%d.union %.2f\n", call, t_union);
+            std::fprintf(stderr, "hga-timing merge%d.device %.2f\n", call, ms(t_groups, clk::now()));
         }
         return merged_ids;
     }
@@ -978,6 +1002,24 @@ std::vector<int> ClusteringEngine::host_read_overlaps(const std::vector<Componen
     return out;
 }
 
+// hga_components_overlaps on the host lists: approximate_read_overlap of each pair.
+std::vector<int> ClusteringEngine::host_component_overlaps(const std::vector<ComponentID>& x,
+                                                           const std::vector<ComponentID>& y) const {
+    if (x.size() != y.size()) throw std::invalid_argument("overlap pairs: x and y differ in length");
+    std::vector<int> out(x.size(), 0);
+    for (size_t q = 0; q < x.size(); ++q) out[q] = approximate_read_overlap(x[q], y[q]);
+    return out;
+}
+
+// hga_components_set_scores on the host lists: accumulate_kmer_ids per set, intersection_size per pair.
+std::vector<Score> ClusteringEngine::host_set_scores(const std::vector<ComponentList>& sets, const SetPairs& pairs) const {
+    std::vector<std::vector<KmerID>> u;
+    for (auto& set : sets) u.push_back(accumulate_kmer_ids(set));
+    std::vector<Score> out;
+    for (auto& pr : pairs) out.push_back(intersection_size(u.at(pr.first), u.at(pr.second)));
+    return out;
+}
+
 // get_spanning_tree_tails (:509-573); ov[q] = approximate_read_overlap of edge q (tree_overlaps).
 std::pair<std::vector<ComponentID>, std::vector<ComponentID>> ClusteringEngine::spanning_tree_tails(
     const SpanningTree& tree, const std::vector<int>& ov) const {
@@ -1052,6 +1094,34 @@ std::vector<std::vector<int>> ClusteringEngine::tree_overlaps(
     for (size_t t = 0; t < ov.size(); ++t) ov[t].assign(comps_and_trees[t].second.size(), -1);   // -1: not computed yet
     ov_edges_dev_ = ov_edges_host_ = 0;
     const char* force_host = std::getenv("HGA_HOST_OVERLAPS");
+    if (dev_sets_ || (sets_mode() && !(force_host && std::string(force_host) == "1"))) {
+        // every edge in one batch on the current component lists (hga_components_overlaps)
+        std::vector<ComponentID> bx, by;
+        for (auto& ct : comps_and_trees)
+            for (auto& edge : ct.second) {
+                bx.push_back(edge.first);
+                by.push_back(edge.second);
+            }
+        if (bx.empty()) return ov;
+        std::vector<int> got;
+        if (dev_cov_) {
+            got = dev_cov_(bx, by);
+            if (got.size() != bx.size()) throw std::runtime_error("device component overlaps: wrong result count");
+        } else {
+            got.resize(bx.size());
+            if (hga_components_overlaps(gpu_, bx.data(), by.data(), bx.size(), got.data(), nullptr) != HGA_OK)
+                throw std::runtime_error(std::string("hga_components_overlaps: ") + hga_last_error());
+        }
+        ++gpu_calls_;
+        size_t i = 0;
+        for (auto& tree_ov : ov)
+            for (int& o : tree_ov) {
+                if (got[i] < 0) throw std::runtime_error("device component overlaps: negative overlap");
+                o = got[i++];
+            }
+        ov_edges_dev_ = bx.size();
+        return ov;
+    }
     if ((dev_ov_ || gpu_) && !(force_host && std::string(force_host) == "1")) {
         std::vector<uint8_t> survivor(reads_.size(), 0);   // by read index: the component was merged into
         for (auto& kv : index_)
@@ -1121,6 +1191,17 @@ std::vector<std::vector<int>> ClusteringEngine::tree_overlaps(
 std::vector<Connection> ClusteringEngine::core_component_connections(
     const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees) {
     std::map<ComponentID, std::pair<std::vector<KmerID>, std::vector<KmerID>>> tails_map;
+    // without host KmerID lists (sets_mode): the ids of each component's two tail sets instead, sets
+    // 2 * slot and 2 * slot + 1 of the one set-score call
+    const bool by_sets = sets_mode();
+    std::map<ComponentID, size_t> tail_slot;
+    std::vector<ComponentList> tail_sets;
+    auto present = [&](const std::vector<ComponentID>& ids) {   // accumulate_kmer_ids skips erased ids
+        ComponentList kept;
+        for (ComponentID id : ids)
+            if (index_.count(id)) kept.push_back(id);
+        return kept;
+    };
     // HGA_TIMING=1: the stage's parts summed over the scaffold components ("hga-timing tails.<part> <ms>")
     using clk = std::chrono::steady_clock;
     double t_tree = 0, t_amp = 0, t_acc = 0;
@@ -1138,11 +1219,56 @@ std::vector<Connection> ClusteringEngine::core_component_connections(
         const auto rv = amplify_component(tails.second, (Score)(int)cfg_.tail_amplification_min_score);
         t_amp += since(t0);
         t0 = clk::now();
-        tails_map.emplace(ct.first[0], std::make_pair(accumulate_kmer_ids(lv), accumulate_kmer_ids(rv)));
+        if (by_sets) {
+            if (tail_slot.emplace(ct.first[0], tail_sets.size() / 2).second) {
+                tail_sets.push_back(present(lv));
+                tail_sets.push_back(present(rv));
+            }
+        } else {
+            tails_map.emplace(ct.first[0], std::make_pair(accumulate_kmer_ids(lv), accumulate_kmer_ids(rv)));
+        }
         t_acc += since(t0);
     }
     const auto t_int0 = clk::now();
     std::vector<Connection> edges;
+    if (by_sets) {
+        SetPairs pairs;
+        for (auto& a : tail_slot)
+            for (auto& b : tail_slot)
+                if (a.first < b.first)
+                    for (uint32_t h = 0; h < 4; ++h)   // left-left, left-right, right-left, right-right (:621-624)
+                        pairs.emplace_back((uint32_t)(2 * a.second + (h >> 1)), (uint32_t)(2 * b.second + (h & 1)));
+        std::vector<Score> sc;
+        if (dev_sets_fn_) {
+            sc = dev_sets_fn_(tail_sets, pairs);
+            if (sc.size() != pairs.size()) throw std::runtime_error("device set scores: wrong result count");
+        } else {
+            std::vector<uint64_t> sp{0};
+            std::vector<uint32_t> ids, pa, pb;
+            for (auto& set : tail_sets) {
+                ids.insert(ids.end(), set.begin(), set.end());
+                sp.push_back(ids.size());
+            }
+            for (auto& pr : pairs) {
+                pa.push_back(pr.first);
+                pb.push_back(pr.second);
+            }
+            sc.resize(pairs.size());
+            if (hga_components_set_scores(gpu_, sp.data(), ids.data(), tail_sets.size(), pa.data(), pb.data(), pairs.size(),
+                                          sc.data(), nullptr) != HGA_OK)
+                throw std::runtime_error(std::string("hga_components_set_scores: ") + hga_last_error());
+        }
+        ++sets_calls_;
+        ++gpu_calls_;
+        size_t at = 0;
+        for (auto& a : tail_slot)
+            for (auto& b : tail_slot)
+                if (a.first < b.first) {
+                    edges.push_back({a.first, b.first, *std::max_element(sc.begin() + (int64_t)at, sc.begin() + (int64_t)at + 4),
+                                     is_good(a.first, b.first)});
+                    at += 4;
+                }
+    }
     for (auto& a : tails_map)
         for (auto& b : tails_map)
             if (a.first < b.first) {
@@ -1153,12 +1279,17 @@ std::vector<Connection> ClusteringEngine::core_component_connections(
                 edges.push_back({a.first, b.first, *std::max_element(s, s + 4), is_good(a.first, b.first)});
             }
     sort_connections(edges);
-    if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1")
+    if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1") {
         std::fprintf(stderr, "hga-timing tails.spanning_tree_tails %.2f\nhga-timing tails.amplify %.2f\n"
                              "hga-timing tails.accumulate %.2f\nhga-timing tails.intersections %.2f\n"
                              "hga-timing tails.overlap_edges_device %llu\nhga-timing tails.overlap_edges_host %llu\n",
-                     t_tree, t_amp, t_acc, since(t_int0), (unsigned long long)ov_edges_dev_,
+                     t_tree, t_amp, t_acc, by_sets ? 0.0 : since(t_int0), (unsigned long long)ov_edges_dev_,
                      (unsigned long long)ov_edges_host_);
+        // (tails.accumulate is then the collection of the set ids, tails.sets_device the one call with its sort)
+        if (by_sets)
+            std::fprintf(stderr, "hga-timing tails.sets_device %.2f\nhga-timing sets.device_calls %llu\n", since(t_int0),
+                         (unsigned long long)sets_calls_);
+    }
     return filter_connections(edges, [](const Connection& c) { return c.score > 0; });
 }
 
@@ -1239,7 +1370,7 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
             if (pristine_ && gpu_) return get_connections({}, s, (uint32_t)std::min<Score>(s, UINT32_MAX));
             std::vector<ComponentID> ids;
             for (auto& kv : index_)
-                if (kv.second.kmers.size() >= s) ids.push_back(kv.first);
+                if (kmer_count(kv.first) >= s) ids.push_back(kv.first);
             return get_connections(ids, s);
         });
         scaffold_forming = filter_connections(conns, [&](const Connection& c) { return c.score > s; });

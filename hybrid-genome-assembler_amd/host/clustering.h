@@ -17,6 +17,10 @@
 // GPU too (hga_read_overlaps), in one batch over all trees, for the edges whose two endpoints were
 // never merged into: those components' KmerID lists are still the reads' own, which is what the
 // device's first-occurrence lists describe.  Edges touching a merge survivor stay on the host.
+// HGA_DEVICE_SETS=1 (opt-in, with the component state on the device) moves the remaining readers of the
+// components' KmerID lists there as well — every tree edge through hga_components_overlaps, the tail
+// sets' unions and intersections through hga_components_set_scores — and the engine then keeps no
+// KmerID list per component at all (see set_device_component_overlaps below).
 //
 // Determinism: the reference iterates tsl::robin_map / std::unordered_map containers and sorts
 // connections with an unstable std::sort on the score only, so ties and container orders are
@@ -148,8 +152,32 @@ class ClusteringEngine {
     // hga_read_overlaps' semantics on the host, from the first-occurrence lists (the hook of the
     // device-less tests): the intersection of the two reads' distinct KmerID lists.
     std::vector<int> host_read_overlaps(const std::vector<ComponentID>& x, const std::vector<ComponentID>& y) const;
+    // The tail stage without host KmerID lists (HGA_DEVICE_SETS=1 with the component state on the
+    // device, or both hooks below set): every spanning-tree edge goes in one batch to
+    // hga_components_overlaps (one call: its kernel takes hga_read_overlaps' path for a never-merged pair
+    // by itself, so splitting the edges would only add a launch, a synchronisation and the bookkeeping),
+    // and core_component_connections makes one hga_components_set_scores call over the amplified left
+    // and right tail vertices of every scaffold component that are still in the index.  Under
+    // HGA_DEVICE_SETS=1 the engine also builds no Component::kmers, its sorted_kid argument may be
+    // empty, and merge_components skips the host union.
+    // fn(x, y) -> approximate_read_overlap of each id pair on the CURRENT component lists.
+    void set_device_component_overlaps(DeviceOverlaps fn) { dev_cov_ = std::move(fn); }
+    // fn(sets, pairs) -> per pair (a, b) of set indices, |accumulate_kmer_ids(sets[a]) ∩ accumulate_kmer_ids(sets[b])|.
+    using SetPairs = std::vector<std::pair<uint32_t, uint32_t>>;
+    using DeviceSetScores = std::function<std::vector<Score>(const std::vector<ComponentList>& sets, const SetPairs& pairs)>;
+    void set_device_set_scores(DeviceSetScores fn) { dev_sets_fn_ = std::move(fn); }
+    // The two hooks' semantics on the host lists (the hooks of the device-less tests).
+    std::vector<int> host_component_overlaps(const std::vector<ComponentID>& x, const std::vector<ComponentID>& y) const;
+    std::vector<Score> host_set_scores(const std::vector<ComponentList>& sets, const SetPairs& pairs) const;
+    // HGA_DEVICE_SETS=1 and neither HGA_HOST_CONNECTIONS=1 nor HGA_HOST_OVERLAPS=1: what an engine with
+    // a ctx runs (the CLI then leaves sorted_kid on the device).
+    static bool device_sets_requested();
+    bool device_sets() const { return dev_sets_; }
+    uint64_t set_score_calls() const { return sets_calls_; }
 
    private:
+    bool sets_mode() const;
+    size_t kmer_count(ComponentID id) const;
     std::vector<KmerID> accumulate_kmer_ids(const std::vector<ComponentID>& ids) const;
     uint32_t kmer_position(ComponentID read, KmerID kid) const;
     uint32_t read_length(ComponentID read) const;
@@ -177,7 +205,10 @@ class ClusteringEngine {
     bool dev_comp_ = false;     // merges and post-merge connections on gpu_ (hga_components_*)
     uint64_t conn_dev_calls_ = 0, conn_host_calls_ = 0;
     DeviceConnections dev_conn_;
-    DeviceOverlaps dev_ov_;
+    DeviceOverlaps dev_ov_, dev_cov_;
+    DeviceSetScores dev_sets_fn_;
+    bool dev_sets_ = false;     // HGA_DEVICE_SETS=1 on the device component state: no KmerID lists here
+    uint64_t sets_calls_ = 0;
     uint64_t ov_edges_dev_ = 0, ov_edges_host_ = 0;
     bool pristine_ = true;   // no merge yet: the device indices still describe the state
     int gpu_calls_ = 0;

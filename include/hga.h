@@ -372,6 +372,31 @@ hga_status hga_components_merge(hga_ctx* ctx, const uint64_t* group_ptr, const u
 hga_status hga_components_connections(hga_ctx* ctx, const uint32_t* pivots, uint64_t n_pivots,
                                       uint64_t min_score, uint64_t* n);
 
+/* approximate_read_overlap (:491-507) on the CURRENT component lists, for n id pairs (x[i], y[i]).  S is
+ * the set of KmerIDs present in both ids' current lists (a survivor's union, any other id's own
+ * sorted_kid slice); shared[i] = |S| counted as distinct KmerIDs; overlap[i] = 0 if S is empty, else the
+ * larger of max - min over S of read_metas[x].kmer_positions and of read_metas[y].kmer_positions, each
+ * id's OWN read, a KmerID the read does not hold reading as 0 (operator[] default; only a union can
+ * contain one).  x[i] == y[i] is allowed; an id without hits gives 0 / 0.  overlap, shared: n entries
+ * each, either may be NULL.  An id outside the lookup's reads: HGA_ERR_INVALID with nothing launched.
+ * n == 0 is HGA_OK.  Before any merge, and after hga_components_reset, equal to hga_read_overlaps.
+ * Synchronous; writes neither the component state nor the lookup's arrays. */
+hga_status hga_components_overlaps(hga_ctx* ctx, const uint32_t* x, const uint32_t* y, uint64_t n,
+                                   int32_t* overlap /* n, may be NULL */, uint32_t* shared /* n, may be NULL */);
+
+/* accumulate_kmer_ids (:341-347) of id groups and the sizes of their pairwise intersections (:621-624).
+ * Set s is ids[set_ptr[s] .. set_ptr[s+1]); U_s is the distinct union of its members' current lists (a
+ * member listed twice or without hits changes nothing; an empty set gives an empty U_s).
+ * set_size[s] = |U_s|; score[p] = |U_pair_a[p] & U_pair_b[p]| (a == b gives |U_a|).
+ * HGA_ERR_INVALID, with nothing launched: an id outside the lookup's reads, a pair index >= n_sets, a
+ * decreasing set_ptr.  n_sets == 0 or n_pairs == 0 is HGA_OK; with n_pairs == 0 the sizes are still
+ * returned.  The sets are bitmap rows within a byte budget (HGA_SETS_BYTES in the environment, read at
+ * call time, overrides it); beyond it the call runs over KmerID tiles.  Synchronous; writes neither the
+ * component state nor the lookup's arrays. */
+hga_status hga_components_set_scores(hga_ctx* ctx, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
+                                     const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                                     uint64_t* score /* n_pairs */, uint64_t* set_size /* n_sets, may be NULL */);
+
 typedef struct hga_components_sizes {
     uint64_t index_entries;   /* entries of the current kmer_component_index                     */
     uint64_t survivors;       /* ids whose list is a union (survived a merge of two or more)     */
