@@ -163,6 +163,13 @@ hga_status hga_components_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t
     HGA_CTX_GUARD(c, hga::components_overlaps(c, x, y, n, overlap, shared));
 }
 
+hga_status hga_tree_tails(hga_ctx* c, const uint64_t* tree_ptr, const uint32_t* ex, const uint32_t* ey, uint64_t n_trees,
+                          const int32_t* overlap, const uint32_t* read_length, uint64_t tail_length, uint64_t* left_ptr,
+                          uint32_t* left, uint64_t* right_ptr, uint32_t* right, hga_tree_ends* ends) {
+    HGA_CTX_GUARD(c, hga::tree_tails(c, tree_ptr, ex, ey, n_trees, overlap, read_length, tail_length, left_ptr, left,
+                                     right_ptr, right, ends));
+}
+
 hga_status hga_components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                                      const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
                                      uint64_t* set_size) {

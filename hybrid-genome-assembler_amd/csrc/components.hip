@@ -807,6 +807,31 @@ void components_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint6
     }
 }
 
+// The ids were validated by the caller; nothing is copied back and the stream is not synchronised.
+void components_overlaps_device(hga_ctx* c, const uint32_t* dx, const uint32_t* dy, uint64_t n, int32_t* dov) {
+    auto& L = c->lookup;
+    auto& S = c->overlap;
+    HGA_REQUIRE(L.ran, HGA_ERR_STATE, "hga_lookup_run not called");
+    if (n == 0) return;
+    ensure_view(c);
+    if (L.hits == 0) {   // no read has a hit: every list is empty
+        HGA_HIP(hipMemsetAsync(dov, 0, n * 4, c->stream));
+        return;
+    }
+    uint32_t* dsh = static_cast<uint32_t*>(S.sh.ensure(std::min(n, CO_CHUNK) * 4));
+    const CmLists lists = lists_of(c);
+    for (uint64_t at = 0; at < n; at += CO_CHUNK) {
+        const uint64_t m = std::min(CO_CHUNK, n - at);
+        const unsigned grid = (unsigned)std::min<uint64_t>((m + 3) / 4, (uint64_t)c->num_cu * 8);
+        c->launch("co_wave", [&] {
+            hipLaunchKernelGGL(co_wave, dim3(grid), dim3(256), 0, c->stream, lists, L.first_ptr.as<uint64_t>(),
+                               L.first_kid.as<uint32_t>(), L.first_pos.as<uint32_t>(), dx + at, dy + at, (uint32_t)m,
+                               L.first_read_id, dov + at, dsh);
+        });
+        c->check_launch("co_wave");
+    }
+}
+
 // One bitmap row per set, a bit per KmerID.  When n_sets rows of all K bits exceed the byte budget the
 // call runs over KmerID tiles of tile_k ids: each tile marks its share of every member list, the pair
 // kernel counts it, and the host adds the tiles' counts up.  A row is never narrower than one 16-byte

@@ -236,6 +236,13 @@ struct ComponentState {
     DevBuf mem, gk, rm, flag, ubuf, seg, ctr, work, rows, scratch;
 };
 
+// hga_tree_tails' work buffers (tails.hip): the edges, the sorted directed edges with their tour, the
+// per-pass weights and the per-tree results
+struct TailsState {
+    DevBuf ex, ey, et, lx, ly, ov, tptr, key, val, sort, where, twin, head, pos, rp, link_a, link_b, w, part, flag_l,
+        flag_r, tmax, tfar, far_id, ptr_l, ptr_r, out_l, out_r;
+};
+
 // Multi-GPU transport of one rank (comm.hip): RCCL over xGMI, or a caller's host-staged hook.
 struct Comm {
     int rank = 0, nranks = 1;
@@ -275,6 +282,7 @@ struct hga_ctx {
     hga::ConnState conn;
     hga::OverlapState overlap;
     hga::ComponentState comp;
+    hga::TailsState tails;
     hga::PinnedBuf pinned;   // small host<->device staging (see count_spec_hist)
     hga::PinnedBuf pinned_sel;   // count_select counters + top-digit histogram
     std::unique_ptr<hga::Comm> comm;   // hga_comm_init*: the count results become global
@@ -357,6 +365,12 @@ void components_drop(hga_ctx* c);
 void components_merge(hga_ctx* c, const uint64_t* group_ptr, const uint32_t* ids, uint64_t n_groups);
 void components_connections(hga_ctx* c, const uint32_t* pivots, uint64_t n_piv, uint64_t min_score, uint64_t* n_out);
 void components_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap, uint32_t* shared);
+// the same for n pairs already on the device (dx, dy, dov: n entries each), enqueued on the ctx stream
+void components_overlaps_device(hga_ctx* c, const uint32_t* dx, const uint32_t* dy, uint64_t n, int32_t* dov);
+// tails.hip: get_spanning_tree_tails of every tree (hga_tree_tails)
+void tree_tails(hga_ctx* c, const uint64_t* tree_ptr, const uint32_t* ex, const uint32_t* ey, uint64_t n_trees,
+                const int32_t* overlap, const uint32_t* read_length, uint64_t tail_length, uint64_t* left_ptr,
+                uint32_t* left, uint64_t* right_ptr, uint32_t* right, hga_tree_ends* ends);
 void components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                            const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
                            uint64_t* set_size);

@@ -45,6 +45,11 @@ class ComponentsSizes(C.Structure):
                 ("merges", C.c_uint64)]
 
 
+class TreeEnds(C.Structure):   # hga_tree_ends
+    _fields_ = [("right_id", C.c_uint32), ("right_dist", C.c_uint64), ("left_id", C.c_uint32),
+                ("left_dist", C.c_uint64)]
+
+
 class LookupResult(C.Structure):
     _fields_ = [("hit_ptr", _u64p), ("hit_kid", _u32p), ("hit_pos", _u32p), ("sorted_kid", _u32p),
                 ("first_ptr", _u64p), ("first_kid", _u32p), ("first_pos", _u32p),
@@ -101,6 +106,8 @@ HGA_SYMBOLS = {
     "hga_components_connections": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint64, _u64p]),
     "hga_components_overlaps": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _i32p, _u32p]),
     "hga_components_set_scores": (C.c_int, [_vp, _u64p, _u32p, C.c_uint64, _u32p, _u32p, C.c_uint64, _u64p, _u64p]),
+    "hga_tree_tails": (C.c_int, [_vp, _u64p, _u32p, _u32p, C.c_uint64, _i32p, _u32p, C.c_uint64, _u64p, _u32p, _u64p,
+                                 _u32p, C.POINTER(TreeEnds)]),
     "hga_components_get_sizes": (C.c_int, [_vp, C.POINTER(ComponentsSizes)]),
     "hga_components_fetch_index": (C.c_int, [_vp, _u64p, _u32p]),
     "hga_components_fetch_kmers": (C.c_int, [_vp, C.c_uint32, _u32p, _u64p]),
@@ -505,6 +512,35 @@ class Ctx:
                                             _p(pb, C.c_uint32), len(pr), _p(score, C.c_uint64), _p(size, C.c_uint64)))
         return score, size
 
+    # ---- spanning-tree tails (get_spanning_tree_tails of every tree in one call)
+    def tree_tails(self, trees, overlap=None, read_length=None, tail_length: int = 0):
+        """trees: a list of edge lists [(x, y), ...].  overlap: one int per edge in the trees' order, or None
+        for hga_components_overlaps' answers on the current component state; read_length: per read of the
+        lookup result (by id - first_read_id), or None for the ctx's own reads.  Returns (left, right, ends):
+        per tree the two ascending id arrays (uint32) and (right_id, right_dist, left_id, left_dist)."""
+        nt = len(trees)
+        tp = np.zeros(nt + 1, np.uint64)
+        tp[1:] = np.cumsum([len(t) for t in trees], dtype=np.uint64)
+        ne = int(tp[nt])
+        xy = np.ascontiguousarray([e for t in trees for e in t], np.uint32).reshape(-1, 2)
+        ex, ey = np.ascontiguousarray(xy[:, 0]), np.ascontiguousarray(xy[:, 1])
+        ov = None if overlap is None else np.ascontiguousarray(overlap, np.int32)
+        if ov is not None and ov.shape != (ne,):
+            raise ValueError("overlap must hold one value per edge")
+        rl = None if read_length is None else np.ascontiguousarray(read_length, np.uint32)
+        if rl is not None and rl.shape != (self.lookup_sizes().n_reads,):
+            raise ValueError("read_length must hold one value per read of the lookup result")
+        lp, rp = np.zeros(nt + 1, np.uint64), np.zeros(nt + 1, np.uint64)
+        left, right = np.zeros(ne + nt, np.uint32), np.zeros(ne + nt, np.uint32)
+        ends = (TreeEnds * max(nt, 1))()
+        _ck(lib().hga_tree_tails(self._h, _p(tp, C.c_uint64), _p(ex, C.c_uint32), _p(ey, C.c_uint32), nt,
+                                 None if ov is None else _p(ov, C.c_int32), None if rl is None else _p(rl, C.c_uint32),
+                                 tail_length, _p(lp, C.c_uint64), _p(left, C.c_uint32), _p(rp, C.c_uint64),
+                                 _p(right, C.c_uint32), ends))
+        return ([left[int(lp[t]):int(lp[t + 1])].copy() for t in range(nt)],
+                [right[int(rp[t]):int(rp[t + 1])].copy() for t in range(nt)],
+                [(e.right_id, e.right_dist, e.left_id, e.left_dist) for e in ends[:nt]])
+
     def components_sizes(self) -> ComponentsSizes:
         s = ComponentsSizes()
         _ck(lib().hga_components_get_sizes(self._h, C.byref(s)))
@@ -798,7 +834,7 @@ def sym_eigen(a):
 
 
 def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None, debug=False, first_read_id=1,
-                 start=None, end=None, batched_overlaps=False, stats=None, device_sets=False):
+                 start=None, end=None, batched_overlaps=False, stats=None, device_sets=False, device_tails=False):
     """run_clustering after construct_indices on the host (no device state): (component ids,
     per-read component id (0 = none), log text).  start / end: the reads' simulator coordinates
     (print_components' intervals under debug), None = 0.
@@ -807,7 +843,9 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
     the host.  stats: a dict that receives "overlap_edges_batched" and "overlap_edges_host".
     device_sets: the tail stage runs the batching of HGA_DEVICE_SETS=1 (every spanning-tree edge in one
     component-overlap call, one set-score call over the tail ids still in the index) through hooks bound
-    to the engine's host implementations."""
+    to the engine's host implementations.
+    device_tails: the tails of all scaffold trees come from one call of the tree-tails hook (the batching of
+    HGA_DEVICE_TAILS=1), bound to the engine's host implementation."""
     L = cluster_lib()
     cfg = cfg or cluster_config()
     off = np.ascontiguousarray(offsets, np.uint64)
@@ -828,7 +866,7 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
                                _p(a["first_kid"], C.c_uint32), _p(a["first_pos"], C.c_uint32), _p(a["kci_ptr"], C.c_uint64),
                                _p(a["kci_read"], C.c_uint32), len(a["kci_ptr"]) - 1, C.byref(cfg), 1 if debug else 0,
                                C.byref(ip), C.byref(ni), C.byref(op), C.byref(lp),
-                               (1 if batched_overlaps else 0) | (2 if device_sets else 0),
+                               (1 if batched_overlaps else 0) | (2 if device_sets else 0) | (4 if device_tails else 0),
                                _p(ove, C.c_uint64)))
     if stats is not None:
         stats["overlap_edges_batched"], stats["overlap_edges_host"] = int(ove[0]), int(ove[1])

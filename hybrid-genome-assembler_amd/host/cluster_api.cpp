@@ -76,7 +76,9 @@ void hgc_free(void* p) { std::free(p); }
 // edge counts {from the batch, from the host's approximate_read_overlap}.  batched is a set of bit flags:
 // 1 is the hook above; 2 sets the component-overlap and set-score hooks (set_device_component_overlaps,
 // set_device_set_scores) to the engine's host implementations, so that the tail stage runs the batching
-// of HGA_DEVICE_SETS=1 (every edge in one call, one set-score call over ids filtered through the index).
+// of HGA_DEVICE_SETS=1 (every edge in one call, one set-score call over ids filtered through the index);
+// 4 sets the tree-tails hook (set_device_tree_tails) to host_tree_tails, so that the tail stage takes the
+// tails of all trees from one call, as under HGA_DEVICE_TAILS=1.
 int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
                 const uint32_t* end, uint64_t n_reads,
                 uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
@@ -123,6 +125,8 @@ int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_
                 return e.host_set_scores(sets, pairs);
             });
         }
+        if (batched & 4)
+            e.set_device_tree_tails([&e](const hgah::ClusteringEngine::TreeList& cts) { return e.host_tree_tails(cts); });
         std::ostringstream log;
         const auto ids = e.run(log);
         if (ov_edges) {

@@ -531,6 +531,11 @@ ClusteringEngine::ClusteringEngine(const ClusteringConfig& cfg, bool debug, cons
     const char* host_conn = std::getenv("HGA_HOST_CONNECTIONS");
     dev_comp_ = gpu_ && !(host_conn && std::string(host_conn) == "1");
     dev_sets_ = dev_comp_ && device_sets_requested();   // the KmerID lists stay on the device
+    dev_tails_ = dev_sets_ && device_tails_requested();
+    if (dev_tails_) {
+        read_len_.resize(n);
+        for (uint64_t i = 0; i < n; ++i) read_len_[i] = (uint32_t)(reads.offsets[i + 1] - reads.offsets[i]);
+    }
     if (!dev_sets_ && sorted_kid.size() != hit_ptr_[n]) throw std::invalid_argument("sorted_kid does not match hit_ptr");
     for (uint64_t i = 0; i < n; ++i) {   // construct_indices :256-276
         if (hit_ptr_[i + 1] == hit_ptr_[i]) continue;
@@ -577,6 +582,13 @@ bool ClusteringEngine::device_sets_requested() {
         return v && std::string(v) == "1";
     };
     return on("HGA_DEVICE_SETS") && !on("HGA_HOST_CONNECTIONS") && !on("HGA_HOST_OVERLAPS");
+}
+
+// HGA_DEVICE_TAILS: 1 the device call, 0 the host passes; unset: the device call (measured faster,
+// DESIGN.md §7).  Only read under HGA_DEVICE_SETS=1.
+bool ClusteringEngine::device_tails_requested() {
+    const char* v = std::getenv("HGA_DEVICE_TAILS");
+    return !(v && std::string(v) == "0");
 }
 
 bool ClusteringEngine::sets_mode() const { return dev_sets_ || (dev_cov_ && dev_sets_fn_); }
@@ -1187,6 +1199,44 @@ std::vector<std::vector<int>> ClusteringEngine::tree_overlaps(
     return ov;
 }
 
+// The tree-tails hook's semantics on the host: the present functions, called per tree.
+ClusteringEngine::TreeTails ClusteringEngine::host_tree_tails(const TreeList& comps_and_trees) {
+    const auto overlaps = tree_overlaps(comps_and_trees);
+    TreeTails out;
+    for (size_t t = 0; t < comps_and_trees.size(); ++t) out.push_back(spanning_tree_tails(comps_and_trees[t].second, overlaps[t]));
+    return out;
+}
+
+// hga_tree_tails over all trees: the edge weights are hga_components_overlaps' on the device, the
+// lengths the flat array built from the reads (valid on a gathered ctx too).
+ClusteringEngine::TreeTails ClusteringEngine::device_tree_tails(const TreeList& comps_and_trees) {
+    std::vector<uint64_t> tp{0};
+    std::vector<uint32_t> ex, ey;
+    for (auto& ct : comps_and_trees) {
+        for (auto& edge : ct.second) {
+            ex.push_back(edge.first);
+            ey.push_back(edge.second);
+        }
+        tp.push_back(ex.size());
+    }
+    const size_t T = comps_and_trees.size();
+    std::vector<uint64_t> lp(T + 1, 0), rp(T + 1, 0);
+    std::vector<uint32_t> left(ex.size() + T), right(ex.size() + T);
+    if (hga_tree_tails(gpu_, tp.data(), ex.data(), ey.data(), T, nullptr, read_len_.data(),
+                       (uint64_t)reads_.meta.avg_read_length * 2, lp.data(), left.data(), rp.data(), right.data(),
+                       nullptr) != HGA_OK)
+        throw std::runtime_error(std::string("hga_tree_tails: ") + hga_last_error());
+    ++gpu_calls_;
+    ov_edges_dev_ = ex.size();
+    ov_edges_host_ = 0;
+    TreeTails out(T);
+    for (size_t t = 0; t < T; ++t) {
+        out[t].first.assign(left.begin() + (int64_t)lp[t], left.begin() + (int64_t)lp[t + 1]);
+        out[t].second.assign(right.begin() + (int64_t)rp[t], right.begin() + (int64_t)rp[t + 1]);
+    }
+    return out;
+}
+
 // get_core_component_connections (:586-651).
 std::vector<Connection> ClusteringEngine::core_component_connections(
     const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees) {
@@ -1207,12 +1257,25 @@ std::vector<Connection> ClusteringEngine::core_component_connections(
     double t_tree = 0, t_amp = 0, t_acc = 0;
     auto since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
     auto t0 = clk::now();
-    const auto overlaps = tree_overlaps(comps_and_trees);
+    // every tree's tails in one call (the hook, or hga_tree_tails on the device's overlaps), else the
+    // batched overlaps and the distance passes per tree
+    const bool one_call = dev_tt_fn_ || dev_tails_;
+    double t_tt = 0;
+    TreeTails all_tails;
+    std::vector<std::vector<int>> overlaps;
+    if (one_call) {
+        all_tails = dev_tt_fn_ ? dev_tt_fn_(comps_and_trees) : device_tree_tails(comps_and_trees);
+        if (all_tails.size() != comps_and_trees.size()) throw std::runtime_error("device tree tails: wrong result count");
+        ++tt_calls_;
+        t_tt = since(t0);
+    } else {
+        overlaps = tree_overlaps(comps_and_trees);
+    }
     t_tree += since(t0);
     for (size_t t = 0; t < comps_and_trees.size(); ++t) {
         auto& ct = comps_and_trees[t];
         t0 = clk::now();
-        const auto tails = spanning_tree_tails(ct.second, overlaps[t]);
+        const auto tails = one_call ? std::move(all_tails[t]) : spanning_tree_tails(ct.second, overlaps[t]);
         t_tree += since(t0);
         t0 = clk::now();
         const auto lv = amplify_component(tails.first, (Score)(int)cfg_.tail_amplification_min_score);
@@ -1289,6 +1352,10 @@ std::vector<Connection> ClusteringEngine::core_component_connections(
         if (by_sets)
             std::fprintf(stderr, "hga-timing tails.sets_device %.2f\nhga-timing sets.device_calls %llu\n", since(t_int0),
                          (unsigned long long)sets_calls_);
+        // (tails.spanning_tree_tails still covers the whole step, this call included)
+        if (one_call)
+            std::fprintf(stderr, "hga-timing tails.tree_tails_device %.2f\nhga-timing tails.tree_tails_calls %llu\n", t_tt,
+                         (unsigned long long)tt_calls_);
     }
     return filter_connections(edges, [](const Connection& c) { return c.score > 0; });
 }

@@ -20,7 +20,9 @@
 // HGA_DEVICE_SETS=1 (opt-in, with the component state on the device) moves the remaining readers of the
 // components' KmerID lists there as well — every tree edge through hga_components_overlaps, the tail
 // sets' unions and intersections through hga_components_set_scores — and the engine then keeps no
-// KmerID list per component at all (see set_device_component_overlaps below).
+// KmerID list per component at all (see set_device_component_overlaps below).  In that mode the three
+// distance passes over every scaffold tree run there as well (hga_tree_tails, one call; HGA_DEVICE_TAILS=0
+// keeps them on the host), so the stage is three device calls that exchange small id lists.
 //
 // Determinism: the reference iterates tsl::robin_map / std::unordered_map containers and sorts
 // connections with an unstable std::sort on the score only, so ties and container orders are
@@ -174,6 +176,21 @@ class ClusteringEngine {
     static bool device_sets_requested();
     bool device_sets() const { return dev_sets_; }
     uint64_t set_score_calls() const { return sets_calls_; }
+    // The spanning-tree tails of every scaffold tree in one call (hga_tree_tails with overlap = NULL and
+    // the reads' lengths): under HGA_DEVICE_SETS=1, HGA_DEVICE_TAILS=1 / 0 selects it / the per-tree host
+    // passes fed by the batched overlaps (unset: the device call).  The call then replaces
+    // tree_overlaps and spanning_tree_tails; the overlaps never reach the host.
+    // fn(components with their trees) -> per tree (left, right), each ascending.
+    using TreeTails = std::vector<std::pair<std::vector<ComponentID>, std::vector<ComponentID>>>;
+    using TreeList = std::vector<std::pair<ComponentList, SpanningTree>>;
+    using DeviceTreeTails = std::function<TreeTails(const TreeList& comps_and_trees)>;
+    void set_device_tree_tails(DeviceTreeTails fn) { dev_tt_fn_ = std::move(fn); }
+    // The hook's semantics on the host (the hook of the device-less tests): the overlaps of every edge as
+    // the engine's mode computes them, then spanning_tree_tails per tree.
+    TreeTails host_tree_tails(const TreeList& comps_and_trees);
+    static bool device_tails_requested();
+    bool device_tails() const { return dev_tails_; }
+    uint64_t tree_tails_calls() const { return tt_calls_; }
 
    private:
     bool sets_mode() const;
@@ -186,6 +203,7 @@ class ClusteringEngine {
     std::vector<std::vector<int>> tree_overlaps(const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees);
     std::pair<std::vector<ComponentID>, std::vector<ComponentID>> spanning_tree_tails(const SpanningTree& tree,
                                                                                       const std::vector<int>& ov) const;
+    TreeTails device_tree_tails(const TreeList& comps_and_trees);
     std::vector<ComponentID> amplify_component(const std::vector<ComponentID>& comp, Score min_score);
     std::vector<Connection> core_component_connections(
         const std::vector<std::pair<ComponentList, SpanningTree>>& comps_and_trees);
@@ -209,6 +227,10 @@ class ClusteringEngine {
     DeviceSetScores dev_sets_fn_;
     bool dev_sets_ = false;     // HGA_DEVICE_SETS=1 on the device component state: no KmerID lists here
     uint64_t sets_calls_ = 0;
+    DeviceTreeTails dev_tt_fn_;
+    bool dev_tails_ = false;    // dev_sets_ and the tree tails through hga_tree_tails
+    std::vector<uint32_t> read_len_;   // by id - first_id_, built once when dev_tails_
+    uint64_t tt_calls_ = 0;
     uint64_t ov_edges_dev_ = 0, ov_edges_host_ = 0;
     bool pristine_ = true;   // no merge yet: the device indices still describe the state
     int gpu_calls_ = 0;

@@ -397,6 +397,47 @@ hga_status hga_components_set_scores(hga_ctx* ctx, const uint64_t* set_ptr, cons
                                      const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
                                      uint64_t* score /* n_pairs */, uint64_t* set_size /* n_sets, may be NULL */);
 
+/* ------------------------------------------------------------------------------
+ * Spanning-tree tails — ReadClusteringEngine::get_spanning_tree_tails
+ * (src/clustering/ReadClusteringEngine.cpp:509-573) for every scaffold tree in one call, under the
+ * fixed orders of host/clustering.h ("Determinism").
+ * Tree t is the edges [tree_ptr[t], tree_ptr[t+1]) of (ex, ey), in either orientation and any order.
+ * Distances (uint64, modulo 2^64 as at :529): dist(start) = length(start), dist(child) = dist(parent) +
+ * length(child) - overlap(parent, child); wrapped values take part in the maxima and thresholds as the
+ * unsigned numbers they are.  Per tree: the first pass starts at the tree's smallest id; "farthest" is the
+ * largest distance, ties to the smallest id; right = the ids with dist + tail_length > max in the pass
+ * started at the first pass's farthest vertex, left = the same in the pass started at that pass's
+ * farthest vertex (the right end); both ascending.  A tree without edges gives two empty lists.
+ * ------------------------------------------------------------------------------ */
+
+/* The two vertices :567-568 prints, with their distances: the farthest vertex of the second pass (right)
+ * and of the third (left); all 0 for a tree without edges. */
+typedef struct hga_tree_ends {
+    uint32_t right_id;
+    uint64_t right_dist;
+    uint32_t left_id;
+    uint64_t left_dist;
+} hga_tree_ends;
+
+/* overlap: one value per edge, sign-extended to 64 bits as (uint64_t)(int64_t) does (negative values are
+ *   legal), or NULL: hga_components_overlaps of every edge on the current component state, computed on
+ *   the device and never copied to the host.
+ * read_length: per read of the current lookup result (by id - first_read_id, n_reads entries), or NULL:
+ *   the lengths of the ctx's own read set; on a gathered ctx of more than one rank (hga_lookup_gather)
+ *   NULL is HGA_ERR_STATE, the other ranks' reads are not there.
+ * left_ptr, right_ptr: n_trees + 1 entries; left, right: caller-allocated, tree_ptr[n_trees] + n_trees
+ *   entries; ends: n_trees entries, may be NULL.
+ * HGA_ERR_INVALID, with the outputs untouched and no state written: a decreasing tree_ptr, an id outside
+ *   the lookup's reads, an id that occurs in two trees, a "tree" that is not one (self-loop, repeated edge
+ *   in either orientation, cycle, more than one connected part).  n_trees == 0 is HGA_OK.
+ * Synchronous; HGA_ERR_STATE before hga_lookup_run; writes neither the component state nor the lookup's
+ * arrays. */
+hga_status hga_tree_tails(hga_ctx* ctx, const uint64_t* tree_ptr, const uint32_t* ex, const uint32_t* ey, uint64_t n_trees,
+                          const int32_t* overlap /* tree_ptr[n_trees] entries, or NULL */,
+                          const uint32_t* read_length /* n_reads, or NULL */, uint64_t tail_length,
+                          uint64_t* left_ptr, uint32_t* left, uint64_t* right_ptr, uint32_t* right,
+                          hga_tree_ends* ends /* n_trees, may be NULL */);
+
 typedef struct hga_components_sizes {
     uint64_t index_entries;   /* entries of the current kmer_component_index                     */
     uint64_t survivors;       /* ids whose list is a union (survived a merge of two or more)     */
