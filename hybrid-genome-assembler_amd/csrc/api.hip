@@ -100,8 +100,9 @@ hga_status hga_ctx_destroy(hga_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
         if (c->side) (void)hipStreamSynchronize(c->side);
         hipStream_t s = c->stream, s2 = c->side;
-        hipEvent_t e1 = c->ev_fork, e2 = c->ev_join;
+        hipEvent_t e1 = c->ev_fork, e2 = c->ev_join, e3 = c->ev_sel;
         delete c;
+        if (e3) (void)hipEventDestroy(e3);
         (void)hipStreamDestroy(s);
         if (s2) {
             (void)hipEventDestroy(e1);

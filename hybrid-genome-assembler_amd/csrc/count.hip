@@ -10,8 +10,8 @@
 //                pick a level-1 region, ranked through LDS so every region's run leaves as
 //                one coalesced segment (>= 512 B); space reserved with one returning atomic
 //                per (tile, region); per-fine-bucket histogram kept in LDS, flushed once.
-//   L  kc_layout one workgroup: fine-bucket bases (bucket-major, file-minor) and the
-//                chunk table of the level-1 regions.
+//   L  kc_layout one scan over the per-workgroup fine histograms read transposed (sort.hip
+//                sc_layout): every (bucket, workgroup) slot range and the per-file bucket runs.
 //   B2 kc_rebin  per 8K-element chunk of a level-1 region: the next fb2 bits pick the fine
 //                bucket (again <= 64-way, coalesced); writes the remainder (u32 when <= 31 bits).
 //   B3 kc_split3 (inputs far above C2 only) per fine bucket: the next fb3 bits pick one of
@@ -427,6 +427,7 @@ __global__ void kc_init_stat(unsigned long long* __restrict__ gstat, uint64_t n_
     if (threadIdx.x < 8) gstat[threadIdx.x] = threadIdx.x == 3 ? (unsigned long long)n_first : 0ull;
 }
 // ---------------------------------------------------------------- layout
+// (more than LAYOUT_W_MAX bin1 workgroups; else sort.hip's layout_scan reads wcnt transposed itself)
 // off[b * W + w] = wcnt[w * nb + b] (64 x 64 LDS tiles), off[nb * W] = 0.  One exclusive scan
 // of off then gives every (fine bucket, workgroup) its first output slot: buckets in order,
 // inside a bucket the workgroups in order (files are workgroup ranges, so file runs are
@@ -709,21 +710,24 @@ __device__ __forceinline__ void rebin_block(const uint64_t blk, const E1* __rest
     }
 }
 
-// first = true: one workgroup per first block (block blockIdx.x < W * nb1); first = false: the spill
-// blocks [W * nb1, gstat[3]) grid-stride over a small grid (at C2 there are none, and a grid of every
-// possible spill block retired ~36 K empty workgroups)
+// One launch: workgroup blockIdx.x < W * nb1 takes that first block; the workgroups appended after
+// them (gridDim.x - W * nb1, at most HGA_SPILL_GRID) take the spill blocks [W * nb1, gstat[3])
+// grid-stride (at C2 there are none, and a grid of every possible spill block retired ~36 K empty
+// workgroups).  First and spill blocks of one chain share their slot range atomically (rebin_block),
+// so their order does not matter.
 template <class E1, class E>
 __global__ void __launch_bounds__(NT_R_MAX) kc_rebin(const E1* __restrict__ in1, const Blk* __restrict__ table,
                                                  const unsigned long long* __restrict__ gstat, uint32_t W,
                                                  KP kp, const uint32_t* __restrict__ nblk,
                                                  unsigned long long* __restrict__ off,
-                                                 E* __restrict__ out, bool first) {
-    if (first) {
+                                                 E* __restrict__ out) {
+    const uint64_t n_first = (uint64_t)W * kp.nb1;
+    if (blockIdx.x < n_first) {
         rebin_block<E1, E>(blockIdx.x, in1, table, W, kp, nblk, off, out);
         return;
     }
-    const uint64_t n_first = (uint64_t)W * kp.nb1, used = gstat[3];
-    for (uint64_t blk = n_first + blockIdx.x; blk < used; blk += gridDim.x) {
+    const uint64_t used = gstat[3], stride = gridDim.x - n_first;
+    for (uint64_t blk = (uint64_t)blockIdx.x; blk < used; blk += stride) {
         rebin_block<E1, E>(blk, in1, table, W, kp, nblk, off, out);
         __syncthreads();   // the block's LDS is reused by the next one
     }
@@ -1996,13 +2000,21 @@ __global__ void __launch_bounds__(256) kc_sel_span(const uint32_t* __restrict__ 
 // the MSD onesweep pass and the 256 one-workgroup LDS segment sorts (C2: 0.16 -> ~0.09 ms); exports
 // with a larger segment keep that path (sort_export_u64).
 constexpr uint32_t BX_MAX = 1024;
+// stat word: 1 when the bucketed sort applies — more than one kept key and no digit total above go_cap
+// (0 with HGA_BX_OFF) — which is the host's own test once the counts are back.  Its kernels are enqueued
+// before the host knows (count_select) and every workgroup of them returns at once on 0.
+constexpr uint32_t BX_GO = 6;
+// The test itself, one definition for kc_bx_prep, kc_bx_colscan<true> and the host: n kept keys, m the
+// largest digit total.
+__host__ __device__ inline bool bx_go(uint64_t n, uint64_t m, uint64_t go_cap) { return n > 1 && m <= go_cap; }
 // One 1024-thread workgroup: dbase[d] = exclusive scan of the digit totals hist[d]; stat[0] / [1] =
 // kept / discriminative keys (the per-workgroup counts wcnt), stat[2] = the largest digit total;
-// stat[0..3] also into the host's mapped staging hstat.
+// stat[0..3] also into the host's mapped staging hstat; stat[BX_GO].  (The path of a select with a
+// hook before its synchronisation; else kc_bx_colscan<true> does this itself.)
 __global__ void __launch_bounds__(1024) kc_bx_prep(const uint32_t* __restrict__ hist, const unsigned long long* __restrict__ wcnt,
                                                    uint32_t grid, uint32_t* __restrict__ dbase,
                                                    unsigned long long* __restrict__ stat,
-                                                   unsigned long long* __restrict__ hstat) {
+                                                   unsigned long long* __restrict__ hstat, uint64_t go_cap) {
     __shared__ uint32_t ws[1024 / 64 + 1];
     __shared__ unsigned long long red[3][16];
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -2043,19 +2055,94 @@ __global__ void __launch_bounds__(1024) kc_bx_prep(const uint32_t* __restrict__ 
         stat[t] = v;
         hstat[t] = v;
     }
+    if (t == 0) {   // the bucketed sort's go / no-go word, the host's own test (count_select's bx)
+        unsigned long long n = 0, m = 0;
+        for (int w = 0; w < 16; ++w) {
+            n += red[0][w];
+            m = max(m, red[2][w]);
+        }
+        stat[BX_GO] = bx_go(n, m, go_cap) ? 1ull : 0ull;
+    }
 }
 // off[w][d] = dbase[d] + sum over workgroups w' < w of their digit-d counts (rows[w'][d]); one
-// workgroup per 16 digits, 16 row groups of threads.
+// workgroup per 16 digits, 16 row groups of threads.  Returns at once unless stat[BX_GO].
+// PREP (no kc_bx_prep ran: the select without a hook, which enqueues this kernel before the host has the
+// counts): every workgroup first scans the SEL_HB digit totals hist itself (16 KB out of L2) for the kept
+// count, the largest total — go / no-go, the same in every workgroup — and the bases of its 16 digits, which
+// it writes to dbase; workgroup 0 also writes what kc_bx_prep writes to stat and hstat.
+template <bool PREP>
 __global__ void __launch_bounds__(256) kc_bx_colscan(const uint32_t* __restrict__ rows, uint32_t n_rows,
-                                                     const uint32_t* __restrict__ dbase, uint32_t* __restrict__ off) {
+                                                     uint32_t* __restrict__ dbase, uint32_t* __restrict__ off,
+                                                     unsigned long long* __restrict__ stat,
+                                                     const uint32_t* __restrict__ hist,
+                                                     const unsigned long long* __restrict__ wcnt,
+                                                     unsigned long long* __restrict__ hstat, uint64_t go_cap) {
     __shared__ uint32_t part[16][17];
+    __shared__ uint32_t s_db[16];
+    if constexpr (PREP) {
+        static_assert(SEL_HB == 256 * 16, "one thread per 16 digit totals");
+        __shared__ uint32_t ws[256 / 64 + 1];
+        __shared__ uint32_t s_mx[4];
+        __shared__ unsigned long long red[2][4];
+        const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        uint32_t h[16], sum = 0, mx = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint4 v = reinterpret_cast<const uint4*>(hist)[4 * t + q];
+            h[4 * q] = v.x; h[4 * q + 1] = v.y; h[4 * q + 2] = v.z; h[4 * q + 3] = v.w;
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            sum += h[q];
+            mx = max(mx, h[q]);
+        }
+        uint32_t tot;
+        uint32_t o = block_excl_scan<256>(sum, ws, &tot);
+        if (t == blockIdx.x) {   // this workgroup's 16 digits
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                s_db[q] = o;
+                dbase[16 * t + q] = o;
+                o += h[q];
+            }
+        }
+        unsigned long long k = 0, dc = 0;
+        if (blockIdx.x == 0)
+            for (uint32_t i = t; i < n_rows; i += 256) {
+                k += wcnt[2 * i];
+                dc += wcnt[2 * i + 1];
+            }
+#pragma unroll
+        for (int s2 = 32; s2; s2 >>= 1) {
+            mx = max(mx, (uint32_t)__shfl_xor(mx, s2, 64));
+            k += __shfl_xor(k, s2, 64);
+            dc += __shfl_xor(dc, s2, 64);
+        }
+        if (lane == 0) {
+            s_mx[wave] = mx;
+            red[0][wave] = k;
+            red[1][wave] = dc;
+        }
+        __syncthreads();
+        const uint32_t m = max(max(s_mx[0], s_mx[1]), max(s_mx[2], s_mx[3]));
+        const bool go = bx_go(tot, m, go_cap);   // (tot: every kept key is counted in one digit)
+        if (blockIdx.x == 0 && t < 4) {
+            const unsigned long long v = t == 2 ? m : t < 2 ? red[t][0] + red[t][1] + red[t][2] + red[t][3] : 0ull;
+            stat[t] = v;
+            hstat[t] = v;
+            if (t == 0) stat[BX_GO] = go ? 1ull : 0ull;
+        }
+        if (!go) return;
+    } else {
+        if (!stat[BX_GO]) return;
+    }
     const uint32_t dl = threadIdx.x & 15, rg = threadIdx.x >> 4, d = blockIdx.x * 16 + dl;
     const uint32_t per = (n_rows + 15) / 16, r0 = rg * per, r1 = min(n_rows, r0 + per);
     uint32_t s2 = 0;
     for (uint32_t r = r0; r < r1; ++r) s2 += rows[(uint64_t)r * SEL_HB + d];
     part[rg][dl] = s2;
     __syncthreads();
-    uint32_t base = dbase[d];
+    uint32_t base = PREP ? s_db[dl] : dbase[d];
     for (uint32_t g = 0; g < rg; ++g) base += part[g][dl];
     for (uint32_t r = r0; r < r1; ++r) {
         off[(uint64_t)r * SEL_HB + d] = base;
@@ -2068,8 +2155,10 @@ __global__ void __launch_bounds__(256) kc_bx_colscan(const uint32_t* __restrict_
 __global__ void __launch_bounds__(256) kc_bx_scatter(const uint64_t* __restrict__ wkeys, uint64_t region,
                                                      const unsigned long long* __restrict__ wcnt,
                                                      const uint32_t* __restrict__ off, int hshift,
-                                                     uint64_t* __restrict__ out) {
+                                                     uint64_t* __restrict__ out,
+                                                     const unsigned long long* __restrict__ stat) {
     __shared__ uint32_t cur[SEL_HB];
+    if (!stat[BX_GO]) return;   // (uniform: nothing is written to out on no-go)
     const uint32_t w = blockIdx.x;
     for (uint32_t i = threadIdx.x; i < SEL_HB; i += 256) cur[i] = off[(uint64_t)w * SEL_HB + i];
     __syncthreads();
@@ -2125,7 +2214,9 @@ __device__ __forceinline__ void bx_sort_seg32(uint64_t* __restrict__ keys, uint3
     }
 }
 __global__ void __launch_bounds__(256) kc_bx_wsort(uint64_t* __restrict__ keys, const uint32_t* __restrict__ hist,
-                                                   const uint32_t* __restrict__ dbase, int bits) {
+                                                   const uint32_t* __restrict__ dbase, int bits,
+                                                   const unsigned long long* __restrict__ stat) {
+    if (!stat[BX_GO]) return;
     const uint32_t d = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint32_t len = hist[d], st = dbase[d];
     if (len <= 1 || len > BX_MAX) return;   // (larger segments: kc_bx_lsort)
@@ -2399,15 +2490,18 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     uint32_t* nblk = static_cast<uint32_t*>(s.nblk.ensure((size_t)std::max<uint32_t>(W, 1) * nb1 * 4));
     for (uint32_t f = 0; f < F; ++f) bf[f].seq = s.seq[f]->as<uint8_t>();
     // per-file tables: uploaded only when they change (they are fixed for repeated runs)
+    // [BinFile x F | the files' first workgroups w0 x F (the layout scan's file starts)]
     const size_t tb = sizeof(BinFile) * F;
-    std::vector<char> tab(tb);
+    std::vector<char> tab(tb + 4 * (size_t)F);
     std::memcpy(tab.data(), bf.data(), tb);
-    char* d_tab = static_cast<char*>(s.bin_files.ensure(tb));
+    for (uint32_t f = 0; f < F; ++f) std::memcpy(tab.data() + tb + 4 * (size_t)f, &bf[f].w0, 4);
+    char* d_tab = static_cast<char*>(s.bin_files.ensure(tab.size()));
     if (s.tab_host != tab) {
-        HGA_HIP(hipMemcpy(d_tab, tab.data(), tb, hipMemcpyHostToDevice));
+        HGA_HIP(hipMemcpy(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
         s.tab_host = tab;
     }
     BinFile* d_bf = reinterpret_cast<BinFile*>(d_tab);
+    const uint32_t* d_w0 = reinterpret_cast<const uint32_t*>(d_tab + tb);
 
     const size_t esz1 = e1_32 ? 4 : 8, esz = e32 ? 4 : 8;
     uint64_t cap = (total_bytes / std::max<uint32_t>(1, min_per_file) + 4) & ~3ull;   // x4: 16-B row groups
@@ -2447,32 +2541,31 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
         });
         c->check_launch("kc_bin1");
     }
-    // L: (bucket, workgroup) output offsets and per-file bucket runs
-    c->launch("kc_layout", [&] {
-        hipLaunchKernelGGL(kc_transpose, dim3(blocks_for(nb, 64), blocks_for(std::max<uint32_t>(W, 1), 64)), dim3(256),
-                           0, c->stream, wcnt, W, nb, reinterpret_cast<uint64_t*>(off));
-    });
-    c->check_launch("kc_transpose");
-    exclusive_scan_u64(c, reinterpret_cast<uint64_t*>(off), (uint64_t)W * nb + 1, s.scratch);
-    c->launch("kc_layout", [&] {
-        hipLaunchKernelGGL(kc_fs, dim3(blocks_for((uint64_t)nb * (F + 1), 256)), dim3(256), 0, c->stream,
-                           reinterpret_cast<const uint64_t*>(off), d_bf, W, nb, F, fs);
-    });
-    c->check_launch("kc_fs");
-    // B2: re-bin every level-1 block into the fine buckets: the first blocks, then the spill blocks
+    // L: (bucket, workgroup) output offsets and per-file bucket runs: one scan launch that reads the fine
+    // histograms transposed (sort.hip layout_scan); with more bin1 workgroups than it takes (C4-sized
+    // inputs), the transposed copy, the scan and kc_fs
+    if (std::getenv("HGA_LAYOUT_T") ||   // (HGA_LAYOUT_T: the three-launch path on any input, tests)
+        !layout_scan(c, wcnt, W, nb, reinterpret_cast<uint64_t*>(off), d_w0, F, fs)) {
+        c->launch("kc_layout", [&] {
+            hipLaunchKernelGGL(kc_transpose, dim3(blocks_for(nb, 64), blocks_for(std::max<uint32_t>(W, 1), 64)),
+                               dim3(256), 0, c->stream, wcnt, W, nb, reinterpret_cast<uint64_t*>(off));
+        });
+        c->check_launch("kc_transpose");
+        exclusive_scan_u64(c, reinterpret_cast<uint64_t*>(off), (uint64_t)W * nb + 1, s.scratch);
+        c->launch("kc_layout", [&] {
+            hipLaunchKernelGGL(kc_fs, dim3(blocks_for((uint64_t)nb * (F + 1), 256)), dim3(256), 0, c->stream,
+                               reinterpret_cast<const uint64_t*>(off), d_bf, W, nb, F, fs);
+        });
+        c->check_launch("kc_fs");
+    }
+    // B2: re-bin every level-1 block into the fine buckets: one workgroup per first block and, behind
+    // them in the same launch, a small grid over the spill blocks
     const unsigned spill_grid = (unsigned)std::min<uint64_t>(table_cap - n_first, HGA_SPILL_GRID);
     c->launch("kc_rebin", [&] {
 #define HGA_REBIN(E1T, ET)                                                                                 \
-    do {                                                                                                   \
-        if (n_first)                                                                                       \
-            hipLaunchKernelGGL((kc_rebin<E1T, ET>), dim3((unsigned)n_first), dim3(rebin_nt<ET>()), 0, c->stream, \
-                               static_cast<const E1T*>(binned1), table, gstat, W, kp, nblk, off,            \
-                               static_cast<ET*>(binned), true);                                              \
-        if (spill_grid)                                                                                    \
-            hipLaunchKernelGGL((kc_rebin<E1T, ET>), dim3(spill_grid), dim3(rebin_nt<ET>()), 0, c->stream,  \
-                               static_cast<const E1T*>(binned1), table, gstat, W, kp, nblk, off,            \
-                               static_cast<ET*>(binned), false);                                             \
-    } while (0)
+    hipLaunchKernelGGL((kc_rebin<E1T, ET>), dim3((unsigned)n_first + spill_grid), dim3(rebin_nt<ET>()), 0,  \
+                       c->stream, static_cast<const E1T*>(binned1), table, gstat, W, kp, nblk, off,        \
+                       static_cast<ET*>(binned))
         if (e1_32 && e32) HGA_REBIN(uint32_t, uint32_t);
         else if (e32) HGA_REBIN(uint64_t, uint32_t);
         else if (e1_32) HGA_REBIN(uint32_t, uint64_t);
@@ -2769,10 +2862,10 @@ void count_spec_hist(hga_ctx* c, const double* thr_in, uint32_t n_thr_in, std::v
     const uint64_t rows_hint = pend ? s.rows_cap : s.rows;
     const unsigned grid = (unsigned)std::min<uint64_t>(blocks_for(std::max<uint64_t>((rows_hint + 3) / 4, 1), NT_S * SG_S),
                                                        (uint64_t)c->num_cu);
+    const unsigned long long* run = pend ? static_cast<const unsigned long long*>(s.cursor.p) : nullptr;
     c->launch("kc_spec_hist", [&] {
         hipLaunchKernelGGL(kc_spec_hist, dim3(grid), dim3(NT_S), (size_t)n_thr * TL * 4, c->stream,
-                           s.rows_cnt.as<uint32_t>(), rows_hint,
-                           pend ? static_cast<const unsigned long long*>(s.cursor.p) : nullptr, s.rows_cap, s.n_files,
+                           s.rows_cnt.as<uint32_t>(), rows_hint, run, s.rows_cap, s.n_files,
                            dthr, n_thr, use_bnd ? (const uint4*)dbnd : nullptr,
                            hist, over, ctrl, over_cap);
     });
@@ -2787,8 +2880,7 @@ void count_spec_hist(hga_ctx* c, const double* thr_in, uint32_t n_thr_in, std::v
         if (before_publish) (*before_publish)(ctrl, comp);
         // one synchronisation: counters and (speculatively) the first chunk of triples together,
         // written into the mapped staging by the kernels themselves
-        hipLaunchKernelGGL(kc_spec_publish, dim3(1), dim3(64), 0, c->stream, ctrl,
-                           pend ? static_cast<const unsigned long long*>(s.cursor.p) : nullptr, c->pinned.dev(hc),
+        hipLaunchKernelGGL(kc_spec_publish, dim3(1), dim3(64), 0, c->stream, ctrl, run, c->pinned.dev(hc),
                            c->pinned.dev(hrun));
     });
     c->check_launch("kc_hist_compact");
@@ -2880,16 +2972,59 @@ void count_select(hga_ctx* c, int64_t lower, int64_t upper, uint64_t* n_out, uin
     auto* hs = reinterpret_cast<unsigned long long*>(hp);
     uint32_t* h256 = reinterpret_cast<uint32_t*>(hp + 64);
     if (!s.rows) HGA_HIP(hipMemsetAsync(stat, 0, 64, c->stream));   // else kc_select clears stat and dhist
+    // bucketed export sort while every 12-bit digit segment fits one workgroup's LDS sort (C2: all of them
+    // fit one wave's registers; a C4 rank shard's ~12 K-key segments take kc_bx_lsort)
+    const bool u32seg = bits - 12 + 1 <= 32;
+    const bool bx_on = !std::getenv("HGA_BX_OFF");
+    const uint64_t go_cap = bx_on ? (u32seg ? (uint64_t)BX_CAP32 : (uint64_t)SS_CAP) : 0ull;
+    // The sort's first three kernels are enqueued before the host has the counts, so the GPU does not idle
+    // over the host's wake-up: they test the same condition on the device (BX_GO) and return at once
+    // when it fails, leaving `out` untouched for the fallbacks below.  A hook before the synchronisation
+    // keeps the order kc_bx_prep, hook, synchronisation, sort.
+    // The host waits for the counts alone (an event behind kc_bx_colscan), not for the scatter and the
+    // segment sorts: they run while the host wakes up, returns and enqueues the caller's next call, as they
+    // did when they were enqueued after the synchronisation.
+    const bool spec = s.rows && msd && bx_on && !before_sync;
+    bool ev_counts = false;
+    auto bx_front = [&](bool prep) {   // digit segments straight from the workgroup regions
+        c->launch("bx_colscan", [&] {
+            if (prep)
+                hipLaunchKernelGGL(kc_bx_colscan<true>, dim3(SEL_HB / 16), dim3(256), 0, c->stream,
+                                   (const uint32_t*)dhist_rows, grid, bx_dbase, bx_off, stat, (const uint32_t*)dhist,
+                                   (const unsigned long long*)wcnt, c->pinned_sel.dev(hs), go_cap);
+            else
+                hipLaunchKernelGGL(kc_bx_colscan<false>, dim3(SEL_HB / 16), dim3(256), 0, c->stream,
+                                   (const uint32_t*)dhist_rows, grid, bx_dbase, bx_off, stat, (const uint32_t*)dhist,
+                                   (const unsigned long long*)wcnt, c->pinned_sel.dev(hs), go_cap);
+        });
+        if (prep) {   // the counts are in the staging once kc_bx_colscan has run: the host waits for that only
+            if (!c->ev_sel) HGA_HIP(hipEventCreateWithFlags(&c->ev_sel, hipEventDisableTiming));
+            HGA_HIP(hipEventRecord(c->ev_sel, c->stream));
+            ev_counts = true;
+        }
+        c->launch("bx_scatter", [&] {
+            hipLaunchKernelGGL(kc_bx_scatter, dim3(grid), dim3(256), 0, c->stream, (const uint64_t*)wkeys, region,
+                               (const unsigned long long*)wcnt, (const uint32_t*)bx_off, bits - 12, out,
+                               (const unsigned long long*)stat);
+        });
+        c->launch("radix_segsort", [&] {
+            hipLaunchKernelGGL(kc_bx_wsort, dim3(SEL_HB / 4), dim3(256), 0, c->stream, out, (const uint32_t*)dhist,
+                               (const uint32_t*)bx_dbase, bits, (const unsigned long long*)stat);
+        });
+        c->check_launch("kc_bx_wsort");
+    };
     if (s.rows) {
         c->launch("kc_select", [&] {
             hipLaunchKernelGGL(kc_select, dim3(grid), dim3(NT_H), 0, c->stream, s.rows_key.as<uint64_t>(),
                                s.rows_cnt.as<uint32_t>(), s.rows, s.rows_cap, s.n_files, lower, upper, wkeys, wflag,
                                flag_bit, cpw, wcnt, dhist_rows, bits - 12, stat, msd ? dhist : nullptr);
-            if (msd) {   // the digit totals, their scan, the counts and the largest digit (kc_bx_prep)
+            if (msd) {   // the digit totals; their scan, the counts and the largest digit: kc_bx_colscan<true>
                 hipLaunchKernelGGL(kc_dhist_reduce, dim3(SEL_HB / 256, (grid + 31) / 32), dim3(256), 0, c->stream,
                                    dhist_rows, grid, dhist);
-                hipLaunchKernelGGL(kc_bx_prep, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)dhist,
-                                   (const unsigned long long*)wcnt, grid, bx_dbase, stat, c->pinned_sel.dev(hs));
+                if (!spec)   // ... or kc_bx_prep
+                    hipLaunchKernelGGL(kc_bx_prep, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)dhist,
+                                       (const unsigned long long*)wcnt, grid, bx_dbase, stat, c->pinned_sel.dev(hs),
+                                       go_cap);
             } else {
                 hipLaunchKernelGGL(kc_sel_compact, dim3(grid), dim3(256), 0, c->stream, (const uint64_t*)wkeys,
                                    (const uint32_t*)wflag, region, (const unsigned long long*)wcnt, grid, out, flag,
@@ -2897,30 +3032,21 @@ void count_select(hga_ctx* c, int64_t lower, int64_t upper, uint64_t* n_out, uin
             }
         });
         c->check_launch("kc_select");
+        if (spec) bx_front(true);
     }
-    // one synchronisation for the counts (kc_bx_prep writes them into the mapped staging; else a copy)
+    // one synchronisation for the counts (kc_bx_prep / kc_bx_colscan<true> write them into the mapped staging;
+    // else a copy)
     if (!(s.rows && msd)) HGA_HIP(hipMemcpyAsync(hs, stat, 64, hipMemcpyDeviceToHost, c->stream));
     if (before_sync) (*before_sync)(stat);
-    c->sync();
+    if (ev_counts) {
+        HGA_HIP(hipEventSynchronize(c->ev_sel));
+    } else {
+        c->sync();
+    }
     const uint64_t n = hs[0];
-    // bucketed export sort while every 12-bit digit segment fits one workgroup's LDS sort (C2: all of them
-    // fit one wave's registers; a C4 rank shard's ~12 K-key segments take kc_bx_lsort)
-    const bool u32seg = bits - 12 + 1 <= 32;
-    const bool bx = msd && n > 1 && hs[2] <= (u32seg ? (uint64_t)BX_CAP32 : (uint64_t)SS_CAP) && !std::getenv("HGA_BX_OFF");
-    if (bx) {   // bucketed export sort: digit segments straight from the workgroup regions
-        c->launch("bx_colscan", [&] {
-            hipLaunchKernelGGL(kc_bx_colscan, dim3(SEL_HB / 16), dim3(256), 0, c->stream, (const uint32_t*)dhist_rows,
-                               grid, (const uint32_t*)bx_dbase, bx_off);
-        });
-        c->launch("bx_scatter", [&] {
-            hipLaunchKernelGGL(kc_bx_scatter, dim3(grid), dim3(256), 0, c->stream, (const uint64_t*)wkeys, region,
-                               (const unsigned long long*)wcnt, (const uint32_t*)bx_off, bits - 12, out);
-        });
-        c->launch("radix_segsort", [&] {
-            hipLaunchKernelGGL(kc_bx_wsort, dim3(SEL_HB / 4), dim3(256), 0, c->stream, out, (const uint32_t*)dhist,
-                               (const uint32_t*)bx_dbase, bits);
-        });
-        c->check_launch("kc_bx_wsort");
+    const bool bx = msd && bx_go(n, hs[2], go_cap);   // (go_cap 0 with HGA_BX_OFF; hs[2] >= 1 when n > 1)
+    if (bx) {
+        if (!spec) bx_front(false);
         if (hs[2] > BX_MAX) {
             c->launch("radix_segsort", [&] {
                 if (u32seg && !std::getenv("HGA_BX_LSD")) {   // (HGA_BX_LSD: the LSD-pass kernels, tests)

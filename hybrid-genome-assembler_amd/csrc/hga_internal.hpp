@@ -267,6 +267,8 @@ struct hga_ctx {
     // the per-read sorts), forked and joined with these two events; created on first use
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // count_select's wait for its counts (recorded behind kc_bx_colscan; created on first use)
+    hipEvent_t ev_sel = nullptr;
     hipStream_t side_stream() {
         if (!side) {
             HGA_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
@@ -442,6 +444,10 @@ void radix_sort_u32_from(hga_ctx* c, const uint32_t* src_k, const uint32_t* src_
                          uint64_t n, int bits, DevBuf& scratch);
 // exclusive scan of u64 in place (sort.hip)
 void exclusive_scan_u64(hga_ctx* c, uint64_t* data, uint64_t n, DevBuf& scratch);
+// count_run's layout in one launch (the scan reads the W x nb histograms transposed and also writes the
+// per-file bucket runs fs; w0: the files' first workgroups, on the device); false: not applicable, nothing done
+bool layout_scan(hga_ctx* c, const uint32_t* wcnt, uint32_t W, uint32_t nb, uint64_t* off, const uint32_t* w0,
+                 uint32_t F, uint64_t* fs);
 // status words + tile-id counter for one chained scan of nt tiles (kmer_dev.hpp chained_lookback)
 struct ScanTicket {
     unsigned long long* status;

@@ -383,6 +383,82 @@ __global__ void __launch_bounds__(SC_T) sc_onepass(T* data, uint64_t n, unsigned
     }
 }
 
+// The count pipeline's layout in one pass: off[b * W + w] = exclusive scan, over that (bucket-major,
+// workgroup-minor) order, of wcnt[w * nb + b] (kc_bin1's row-major fine histograms), off[nb * W] = the
+// total — sc_onepass with a tile load that reads wcnt transposed, so no transposed copy is written and read
+// back.  A tile of SC_TILE consecutive entries covers nbk = SC_TILE / W (+ 2) buckets of every workgroup's
+// row: the reads go out workgroup by workgroup, nbk adjacent counts each (32 B at W = 512), into LDS.
+// The tile that writes entry b * W + w0[f] (file f's first workgroup) or (b + 1) * W also writes it to
+// fs[b * (F + 1) + f] resp. fs[b * (F + 1) + F]: the per-file bucket runs (count.hip kc_fs).  W >= 1.
+__global__ void __launch_bounds__(SC_T) sc_layout(const uint32_t* __restrict__ wcnt, uint32_t W, uint32_t nb,
+                                                  uint64_t* __restrict__ off, const uint32_t* __restrict__ w0,
+                                                  uint32_t F, uint64_t* __restrict__ fs,
+                                                  unsigned long long* __restrict__ status,
+                                                  unsigned long long* __restrict__ ctr, uint64_t tbase, uint32_t epoch) {
+    __shared__ uint64_t ws[SC_T / 64];
+    __shared__ uint64_t s_tile, s_pre;
+    __shared__ uint32_t tv[SC_TILE];
+    __shared__ uint64_t sv[SC_TILE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) s_tile = atomicAdd(ctr, 1ull) - tbase;
+    for (uint32_t l = threadIdx.x; l < (uint32_t)SC_TILE; l += SC_T) tv[l] = 0;
+    __syncthreads();
+    const uint64_t tile = s_tile;
+    const uint64_t n = (uint64_t)W * nb + 1;
+    const uint64_t i0 = tile * SC_TILE, i1 = i0 + SC_TILE < n ? i0 + SC_TILE : n;   // i0 < n: tile < tiles of n
+    const uint64_t ne = i1 < n - 1 ? i1 : n - 1;   // entries [i0, ne) come from wcnt, entry n - 1 is 0
+    const uint32_t b_lo = (uint32_t)(i0 / W);
+    if (ne > i0) {
+        const uint32_t nbk = (uint32_t)((ne - 1) / W) - b_lo + 1;
+        const uint32_t np = W * nbk;   // <= SC_TILE + 2 W
+        for (uint32_t p = threadIdx.x; p < np; p += SC_T) {
+            const uint32_t w = p / nbk, b = b_lo + (p - w * nbk);
+            const uint64_t i = (uint64_t)b * W + w;
+            if (i >= i0 && i < ne) tv[i - i0] = wcnt[(uint64_t)w * nb + b];
+        }
+    }
+    __syncthreads();
+    const uint32_t lb = threadIdx.x * SC_I;
+    uint64_t v[SC_I];
+    uint64_t sum = 0;
+#pragma unroll
+    for (int j = 0; j < SC_I; ++j) {
+        v[j] = tv[lb + j];
+        sum += v[j];
+    }
+    const uint64_t inc = wave_incl_scan64(sum, lane);
+    if (lane == 63) ws[wave] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t agg = 0;
+        for (int w = 0; w < SC_T / 64; ++w) {
+            const uint64_t x = ws[w];
+            ws[w] = agg;
+            agg += x;
+        }
+        s_pre = chained_lookback(status, tile, agg, epoch);
+    }
+    __syncthreads();
+    uint64_t run = s_pre + ws[wave] + inc - sum;
+#pragma unroll
+    for (int j = 0; j < SC_I; ++j) {
+        if (i0 + lb + j < n) off[i0 + lb + j] = run;
+        sv[lb + j] = run;
+        run += v[j];
+    }
+    __syncthreads();
+    // the file starts and bucket ends among this tile's entries: buckets [b_lo - 1, (i1 - 1) / W]
+    const uint32_t bs = b_lo ? b_lo - 1 : 0;
+    const uint64_t bl = (i1 - 1) / W;
+    const uint32_t be = bl < nb ? (uint32_t)bl : nb - 1;   // >= bs (b_lo == nb: the tile of entry n - 1 alone)
+    const uint32_t nc = (be - bs + 1) * (F + 1);
+    for (uint32_t q = threadIdx.x; q < nc; q += SC_T) {
+        const uint32_t b = bs + q / (F + 1), f = q % (F + 1);
+        const uint64_t idx = f == F ? (uint64_t)(b + 1) * W : (uint64_t)b * W + w0[f];
+        if (idx >= i0 && idx < i1) fs[(uint64_t)b * (F + 1) + f] = sv[idx - i0];
+    }
+}
+
 }  // namespace
 
 // Status words and tile ids for nt tiles of one chained scan (chained_lookback): a fresh epoch, the
@@ -642,6 +718,24 @@ void radix_sort_u32_from(hga_ctx* c, const uint32_t* src_k, const uint32_t* src_
 void exclusive_scan_u64(hga_ctx* c, uint64_t* data, uint64_t n, DevBuf& scratch) {
     (void)scratch;   // the single-pass scan keeps its state in the ctx
     excl_scan_impl<uint64_t>(c, data, n);
+}
+
+// The count pipeline's layout (sc_layout): off (W * nb + 1 entries) and fs from the W x nb fine
+// histograms, one launch.  False (nothing enqueued) when W is 0 or above LAYOUT_W_MAX, where a tile's
+// transposed reads would be 4 to 12 bytes each: the caller transposes, scans and derives fs then.
+bool layout_scan(hga_ctx* c, const uint32_t* wcnt, uint32_t W, uint32_t nb, uint64_t* off, const uint32_t* w0,
+                 uint32_t F, uint64_t* fs) {
+    constexpr uint32_t LAYOUT_W_MAX = SC_TILE / 4;
+    if (W == 0 || W > LAYOUT_W_MAX) return false;
+    const uint64_t n = (uint64_t)W * nb + 1;
+    const uint64_t nt = (n + SC_TILE - 1) / SC_TILE;
+    const ScanTicket t = scan_ticket(c, nt);
+    c->launch("kc_layout", [&] {
+        hipLaunchKernelGGL(sc_layout, dim3((unsigned)nt), dim3(SC_T), 0, c->stream, wcnt, W, nb, off, w0, F, fs,
+                           t.status, t.ctr, t.tbase, t.epoch);
+    });
+    c->check_launch("sc_layout");
+    return true;
 }
 
 }  // namespace hga
