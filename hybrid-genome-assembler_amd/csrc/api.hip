@@ -171,6 +171,15 @@ hga_status hga_tree_tails(hga_ctx* c, const uint64_t* tree_ptr, const uint32_t* 
                                      right_ptr, right, ends));
 }
 
+hga_status hga_spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first, uint64_t count,
+                               uint64_t* n_edges) {
+    HGA_CTX_GUARD(c, hga::spanning_forest(c, x, y, n, first, count, n_edges));
+}
+
+hga_status hga_spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uint32_t* y) {
+    HGA_CTX_GUARD(c, hga::spanning_forest_fetch(c, pos, x, y));
+}
+
 hga_status hga_components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                                      const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
                                      uint64_t* set_size) {

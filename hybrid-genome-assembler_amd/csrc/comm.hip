@@ -871,6 +871,7 @@ void lookup_gather(hga_ctx* c) {
     L.reads_hit = g.reads_hit;
     L.gathered = true;
     c->conn.ready = false;
+    c->forest.have = false;
 }
 
 void connections_gather(hga_ctx* c, uint64_t* n_out) {

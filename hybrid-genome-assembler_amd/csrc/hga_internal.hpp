@@ -243,6 +243,15 @@ struct TailsState {
         flag_r, tmax, tfar, far_id, ptr_l, ptr_r, out_l, out_r;
 };
 
+// hga_spanning_forest's buffers (forest.hip): the uploaded edges, the component pointers (double-buffered),
+// the best position per root, the live positions (double-buffered), the accepted positions, and the result
+// hga_spanning_forest_fetch copies (have: a call has succeeded since the last hga_lookup_run)
+struct ForestState {
+    bool have = false;
+    uint64_t n = 0, first = 0;
+    DevBuf ex, ey, comp_a, comp_b, best, live_a, live_b, acc, ctr, sort, pos, x, y;
+};
+
 // Multi-GPU transport of one rank (comm.hip): RCCL over xGMI, or a caller's host-staged hook.
 struct Comm {
     int rank = 0, nranks = 1;
@@ -285,6 +294,7 @@ struct hga_ctx {
     hga::OverlapState overlap;
     hga::ComponentState comp;
     hga::TailsState tails;
+    hga::ForestState forest;
     hga::PinnedBuf pinned;   // small host<->device staging (see count_spec_hist)
     hga::PinnedBuf pinned_sel;   // count_select counters + top-digit histogram
     std::unique_ptr<hga::Comm> comm;   // hga_comm_init*: the count results become global
@@ -373,6 +383,10 @@ void components_overlaps_device(hga_ctx* c, const uint32_t* dx, const uint32_t* 
 void tree_tails(hga_ctx* c, const uint64_t* tree_ptr, const uint32_t* ex, const uint32_t* ey, uint64_t n_trees,
                 const int32_t* overlap, const uint32_t* read_length, uint64_t tail_length, uint64_t* left_ptr,
                 uint32_t* left, uint64_t* right_ptr, uint32_t* right, hga_tree_ends* ends);
+// forest.hip: the connections an uncapped, unrestricted union_find accepts (hga_spanning_forest*)
+void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first, uint64_t count,
+                     uint64_t* n_edges);
+void spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uint32_t* y);
 void components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                            const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
                            uint64_t* set_size);

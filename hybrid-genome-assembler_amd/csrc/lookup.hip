@@ -1322,6 +1322,7 @@ void lookup_run(hga_ctx* c) {
     HGA_REQUIRE(L.loaded, HGA_ERR_STATE, "hga_lookup_load not called");
     HGA_REQUIRE(L.have_reads, HGA_ERR_STATE, "hga_lookup_set_reads not called");
     c->conn.ready = false;
+    c->forest.have = false;
     lookup_pack(c, HGA_LK_ASCII != 0);
     const uint64_t n = L.n_reads, nb = L.n_bases;
     const int k = L.k;

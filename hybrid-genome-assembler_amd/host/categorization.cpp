@@ -242,8 +242,9 @@ int main(int argc, char* argv[]) {
     if (P > 1) {   // the device connection pass with the pivots split over the ranks
         std::vector<int32_t> cats;
         if (engine_debug) cats.assign(rs.category.begin(), rs.category.end());
-        engine.set_device_connections([&](const std::vector<hgah::ComponentID>& pivots, hgah::Score min_score,
-                                          uint32_t min_kmers) {
+        // the ranks' connections of their pivots, joined in the reference order on every ctx; returns their number
+        auto gathered_connections = [&, cats](const std::vector<hgah::ComponentID>& pivots, hgah::Score min_score,
+                                              uint32_t min_kmers) {
             std::vector<uint64_t> ns(P, 0);
             ranks.each([&](int r, hga_ctx* c) {
                 std::vector<uint32_t> piv;
@@ -260,7 +261,11 @@ int main(int argc, char* argv[]) {
                                           engine_debug ? cats.data() : nullptr, &n), "hga_connections_run");
                 check(hga_connections_gather(c, &ns[r]), "hga_connections_gather");
             });
-            const uint64_t n = ns[0];
+            return ns[0];
+        };
+        engine.set_device_connections([&, gathered_connections](const std::vector<hgah::ComponentID>& pivots,
+                                                                hgah::Score min_score, uint32_t min_kmers) {
+            const uint64_t n = gathered_connections(pivots, min_score, min_kmers);
             std::vector<uint32_t> x(n), y(n);
             std::vector<uint64_t> sc(n);
             std::vector<uint8_t> g(n);
@@ -269,6 +274,21 @@ int main(int argc, char* argv[]) {
             for (uint64_t i = 0; i < n; ++i) out[i] = {x[i], y[i], sc[i], g[i] != 0};
             return out;
         });
+        // HGA_DEVICE_FOREST=1: the spanning forest of the gathered list's prefix on the writing rank's ctx
+        if (hgah::ClusteringEngine::device_forest_requested())
+            engine.set_device_forest([&, gathered_connections](hgah::Score min_score, uint32_t min_kmers, double keep_fraction) {
+                uint64_t n = gathered_connections({}, min_score, min_kmers);
+                if (keep_fraction >= 0) n = std::min<uint64_t>(n, (uint64_t)(size_t)((double)n * keep_fraction));
+                uint64_t e = 0;
+                check(hga_spanning_forest(ctx, nullptr, nullptr, 0, 0, n, &e), "hga_spanning_forest");
+                std::vector<uint32_t> x(e), y(e);
+                check(hga_spanning_forest_fetch(ctx, nullptr, x.data(), y.data()), "hga_spanning_forest_fetch");
+                hgah::ClusteringEngine::ForestEdges out;
+                out.connections = n;
+                out.edges.resize(e);
+                for (uint64_t i = 0; i < e; ++i) out.edges[i] = {x[i], y[i]};
+                return out;
+            });
     }
     tm.mark("engine_setup");
     const std::vector<hgah::ComponentID> cluster_ids = engine.run(std::cout);   // run_clustering (:699-802)

@@ -12,6 +12,7 @@
 
 namespace {
 thread_local std::string g_err;
+thread_local uint64_t g_forest_calls = 0;   // of this thread's last hgc_cluster* call (hgc_forest_calls)
 
 template <class F>
 int guard(F&& f) {
@@ -78,7 +79,10 @@ void hgc_free(void* p) { std::free(p); }
 // set_device_set_scores) to the engine's host implementations, so that the tail stage runs the batching
 // of HGA_DEVICE_SETS=1 (every edge in one call, one set-score call over ids filtered through the index);
 // 4 sets the tree-tails hook (set_device_tree_tails) to host_tree_tails, so that the tail stage takes the
-// tails of all trees from one call, as under HGA_DEVICE_TAILS=1.
+// tails of all trees from one call, as under HGA_DEVICE_TAILS=1;
+// 8 sets the spanning-forest hook (set_device_forest) to host_forest, so that the first union_find replays
+// only the connections it would accept, as under HGA_DEVICE_FOREST=1; hgc_forest_calls() then tells how
+// many times this thread's last hgc_cluster* call took that path.
 int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
                 const uint32_t* end, uint64_t n_reads,
                 uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
@@ -127,8 +131,14 @@ int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_
         }
         if (batched & 4)
             e.set_device_tree_tails([&e](const hgah::ClusteringEngine::TreeList& cts) { return e.host_tree_tails(cts); });
+        if (batched & 8)
+            e.set_device_forest([&e](hgah::Score min_score, uint32_t min_kmers, double keep_fraction) {
+                return e.host_forest(min_score, min_kmers, keep_fraction);
+            });
         std::ostringstream log;
+        g_forest_calls = 0;
         const auto ids = e.run(log);
+        g_forest_calls = e.forest_calls();
         if (ov_edges) {
             ov_edges[0] = e.overlap_edges_device();
             ov_edges[1] = e.overlap_edges_host();
@@ -154,6 +164,8 @@ int hgc_cluster(const char* bases, const uint64_t* offsets, const int32_t* categ
                                sorted_kid, first_ptr, first_kid, first_pos, kci_ptr, kci_read, n_sdk, cfg, debug, ids_out,
                                n_ids, comp_of_read, log_out, 0, nullptr);
 }
+
+uint64_t hgc_forest_calls(void) { return g_forest_calls; }
 
 // union_find (ReadClusteringEngine.cpp:424-489) of an ordered connection list.
 int hgc_union_find(const uint32_t* x, const uint32_t* y, const uint64_t* s, uint64_t n, const uint32_t* restricted,

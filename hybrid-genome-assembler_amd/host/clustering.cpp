@@ -532,6 +532,7 @@ ClusteringEngine::ClusteringEngine(const ClusteringConfig& cfg, bool debug, cons
     dev_comp_ = gpu_ && !(host_conn && std::string(host_conn) == "1");
     dev_sets_ = dev_comp_ && device_sets_requested();   // the KmerID lists stay on the device
     dev_tails_ = dev_sets_ && device_tails_requested();
+    dev_forest_ = dev_comp_ && device_forest_requested();
     if (dev_tails_) {
         read_len_.resize(n);
         for (uint64_t i = 0; i < n; ++i) read_len_[i] = (uint32_t)(reads.offsets[i + 1] - reads.offsets[i]);
@@ -589,6 +590,21 @@ bool ClusteringEngine::device_sets_requested() {
 bool ClusteringEngine::device_tails_requested() {
     const char* v = std::getenv("HGA_DEVICE_TAILS");
     return !(v && std::string(v) == "0");
+}
+
+bool ClusteringEngine::device_forest_requested() {
+    auto on = [](const char* name) {
+        const char* v = std::getenv(name);
+        return v && std::string(v) == "1";
+    };
+    return on("HGA_DEVICE_FOREST") && !on("HGA_HOST_CONNECTIONS");
+}
+
+// The uncapped first union_find of a pristine engine (see clustering.h): the hook, else the single ctx
+// (with a multi-rank connection hook set the list is not on gpu_, so only the forest hook answers).
+bool ClusteringEngine::forest_applies() const {
+    return pristine_ && cfg_.scaffold_forming_score == 0 && cfg_.scaffold_component_max_size == -1 &&
+           (dev_forest_fn_ || (dev_forest_ && !dev_conn_));
 }
 
 bool ClusteringEngine::sets_mode() const { return dev_sets_ || (dev_cov_ && dev_sets_fn_); }
@@ -691,13 +707,7 @@ std::vector<Connection> ClusteringEngine::get_connections(const std::vector<Comp
         return prefix(dev_conn_(pivots, min_score, min_kmers));
     }
     // construct_indices' state is on the device: hga_connections_run (connect.hip)
-    std::vector<int32_t> cats;
-    if (debug_) cats.assign(reads_.category.begin(), reads_.category.end());
-    uint64_t n = 0;
-    const bool all = min_kmers > 0;   // every component with >= min_kmers KmerIDs (filter_components)
-    if (hga_connections_run(gpu_, all ? nullptr : pivots.data(), all ? 0 : pivots.size(), all ? min_kmers : 1,
-                            min_score, debug_ ? cats.data() : nullptr, &n) != HGA_OK)
-        throw std::runtime_error(std::string("hga_connections_run: ") + hga_last_error());
+    uint64_t n = device_connections_run(pivots, min_score, min_kmers);
     if (keep_fraction >= 0) n = std::min<uint64_t>(n, (uint64_t)(size_t)((double)n * keep_fraction));
     std::vector<uint32_t> x(n), y(n);
     std::vector<uint64_t> s(n);
@@ -707,6 +717,61 @@ std::vector<Connection> ClusteringEngine::get_connections(const std::vector<Comp
     ++gpu_calls_;
     std::vector<Connection> out(n);
     for (uint64_t i = 0; i < n; ++i) out[i] = {x[i], y[i], s[i], g[i] != 0};
+    return out;
+}
+
+uint64_t ClusteringEngine::device_connections_run(const std::vector<ComponentID>& pivots, Score min_score,
+                                                  uint32_t min_kmers) {
+    std::vector<int32_t> cats;
+    if (debug_) cats.assign(reads_.category.begin(), reads_.category.end());
+    uint64_t n = 0;
+    const bool all = min_kmers > 0;   // every component with >= min_kmers KmerIDs (filter_components)
+    if (hga_connections_run(gpu_, all ? nullptr : pivots.data(), all ? 0 : pivots.size(), all ? min_kmers : 1,
+                            min_score, debug_ ? cats.data() : nullptr, &n) != HGA_OK)
+        throw std::runtime_error(std::string("hga_connections_run: ") + hga_last_error());
+    return n;
+}
+
+// The sorted list stays on the device; only the connections union_find would accept come back.
+ClusteringEngine::ForestEdges ClusteringEngine::device_forest(Score min_score, uint32_t min_kmers, double keep_fraction) {
+    uint64_t n = device_connections_run({}, min_score, min_kmers);
+    if (keep_fraction >= 0) n = std::min<uint64_t>(n, (uint64_t)(size_t)((double)n * keep_fraction));
+    ++gpu_calls_;
+    uint64_t e = 0;
+    if (hga_spanning_forest(gpu_, nullptr, nullptr, 0, 0, n, &e) != HGA_OK)
+        throw std::runtime_error(std::string("hga_spanning_forest: ") + hga_last_error());
+    std::vector<uint32_t> x(e), y(e);
+    if (hga_spanning_forest_fetch(gpu_, nullptr, x.data(), y.data()) != HGA_OK)
+        throw std::runtime_error(std::string("hga_spanning_forest_fetch: ") + hga_last_error());
+    ForestEdges out;
+    out.connections = n;
+    out.edges.resize(e);
+    for (uint64_t i = 0; i < e; ++i) out.edges[i] = {x[i], y[i]};
+    return out;
+}
+
+ClusteringEngine::ForestEdges ClusteringEngine::host_forest(Score min_score, uint32_t min_kmers, double keep_fraction) {
+    (void)min_kmers;   // (1 on this path: every component of the index is a pivot, as in get_all_connections)
+    const std::vector<Connection> conns = get_all_connections(min_score, keep_fraction);
+    ForestEdges out;
+    out.connections = conns.size();
+    std::unordered_map<ComponentID, ComponentID> parent;
+    auto root = [&](ComponentID v) {
+        ComponentID r = parent.emplace(v, v).first->second;
+        while (parent[r] != r) r = parent[r];
+        while (parent[v] != r) {
+            const ComponentID nx = parent[v];
+            parent[v] = r;
+            v = nx;
+        }
+        return r;
+    };
+    for (const Connection& c : conns) {
+        const ComponentID px = root(c.x), py = root(c.y);
+        if (px == py) continue;
+        parent[px] = py;
+        out.edges.emplace_back(c.x, c.y);
+    }
     return out;
 }
 
@@ -1441,6 +1506,18 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
             return get_connections(ids, s);
         });
         scaffold_forming = filter_connections(conns, [&](const Connection& c) { return c.score > s; });
+    } else if (forest_applies()) {
+        // the prefix stays on the device: only the connections union_find accepts come back, in position
+        // order, and its replay over them repeats the full list's merges (clustering.h)
+        const ForestEdges fe = timed(out, "Calculation of connections between reads", [&] {
+            const double f = cfg_.scaffold_forming_fraction;
+            return dev_forest_fn_ ? dev_forest_fn_(1, 1, f) : device_forest(1, 1, f);
+        });
+        ++forest_calls_;
+        forest_conns_ = fe.connections;
+        forest_edges_ = fe.edges.size();
+        scaffold_forming.reserve(fe.edges.size());
+        for (auto& e : fe.edges) scaffold_forming.push_back({e.first, e.second, 0, false});
     } else {
         // only the first size * fraction entries are used (:754-755): fetch just that prefix
         scaffold_forming = timed(out, "Calculation of connections between reads",
@@ -1479,6 +1556,10 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
     if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1")
         std::fprintf(stderr, "hga-timing conn.device_calls %llu\nhga-timing conn.host_calls %llu\n",
                      (unsigned long long)conn_dev_calls_, (unsigned long long)conn_host_calls_);
+    if (const char* te = std::getenv("HGA_TIMING"); forest_calls_ && te && std::string(te) == "1")
+        std::fprintf(stderr, "hga-timing forest.device_calls %llu\nhga-timing forest.connections %llu\nhga-timing forest.edges %llu\n",
+                     (unsigned long long)forest_calls_, (unsigned long long)forest_conns_,
+                     (unsigned long long)forest_edges_);
     return core_ids;
 }
 

@@ -191,8 +191,34 @@ class ClusteringEngine {
     static bool device_tails_requested();
     bool device_tails() const { return dev_tails_; }
     uint64_t tree_tails_calls() const { return tt_calls_; }
+    // The first union_find call from a spanning forest (HGA_DEVICE_FOREST=1, opt-in).  With
+    // scaffold_component_max_size = -1 and nothing restricted the loop (:424-489) rejects a connection only
+    // when both ends are already in one component, so the accepted connections are the minimum spanning
+    // forest of the list with the position as weight, and replaying union_find over them alone, in
+    // position order, repeats the full list's merges (every other connection was a no-op).  run() then
+    // leaves the sorted list on the device, has hga_spanning_forest find the accepted connections of the
+    // scaffold-forming prefix and fetches only those (at most n_reads - 1) for the unchanged union_find.
+    // Applies while the engine is pristine with a ctx (or the hook below), on the fraction path
+    // (scaffold_forming_score == 0) with scaffold_component_max_size == -1; every other call runs as before.
+    // fn(min_score, min_kmers, keep_fraction) -> the accepted (x, y) in position order and the prefix length.
+    struct ForestEdges {
+        SpanningTree edges;
+        uint64_t connections = 0;   // the scaffold-forming prefix they were taken from
+    };
+    using DeviceForest = std::function<ForestEdges(Score min_score, uint32_t min_kmers, double keep_fraction)>;
+    void set_device_forest(DeviceForest fn) { dev_forest_fn_ = std::move(fn); }
+    // The hook's semantics on the host (the hook of the device-less tests): get_all_connections' prefix,
+    // then the connections that join two components.
+    ForestEdges host_forest(Score min_score, uint32_t min_kmers, double keep_fraction);
+    // HGA_DEVICE_FOREST=1 without HGA_HOST_CONNECTIONS=1: what an engine with a ctx runs.
+    static bool device_forest_requested();
+    uint64_t forest_calls() const { return forest_calls_; }
 
    private:
+    bool forest_applies() const;
+    ForestEdges device_forest(Score min_score, uint32_t min_kmers, double keep_fraction);
+    // hga_connections_run of the pristine state as get_connections calls it; returns the list's length
+    uint64_t device_connections_run(const std::vector<ComponentID>& pivots, Score min_score, uint32_t min_kmers);
     bool sets_mode() const;
     size_t kmer_count(ComponentID id) const;
     std::vector<KmerID> accumulate_kmer_ids(const std::vector<ComponentID>& ids) const;
@@ -231,6 +257,9 @@ class ClusteringEngine {
     bool dev_tails_ = false;    // dev_sets_ and the tree tails through hga_tree_tails
     std::vector<uint32_t> read_len_;   // by id - first_id_, built once when dev_tails_
     uint64_t tt_calls_ = 0;
+    DeviceForest dev_forest_fn_;
+    bool dev_forest_ = false;   // HGA_DEVICE_FOREST=1 with the component state on the device
+    uint64_t forest_calls_ = 0, forest_conns_ = 0, forest_edges_ = 0;
     uint64_t ov_edges_dev_ = 0, ov_edges_host_ = 0;
     bool pristine_ = true;   // no merge yet: the device indices still describe the state
     int gpu_calls_ = 0;

@@ -456,6 +456,43 @@ hga_status hga_components_fetch_kmers(hga_ctx* ctx, uint32_t id, uint32_t* kmers
 hga_status hga_components_reset(hga_ctx* ctx);
 
 /* ------------------------------------------------------------------------------
+ * Spanning forest — the connections union_find accepts
+ * (src/clustering/ReadClusteringEngine.cpp:424-489) when it has no rejection rule beyond "same
+ * component": max_component_size = -1 and no restricted id, the first call of run_clustering in the
+ * default configuration (:754-761).  The loop is Kruskal's over the list in order, so with an edge's
+ * weight its position in the list (all distinct) the accepted edges are the unique minimum spanning
+ * forest of the multigraph, and the device finds them in parallel (Boruvka rounds).
+ * Replaying union_find over the accepted edges alone, in position order, gives the merge sequence
+ * of the full list: every other connection found get_parent(x) == get_parent(y) and changed
+ * nothing.  So the ComponentList member order (merge_components keeps the first member, :366), the
+ * SpanningTree edge order and the order of the result are the same, and a caller fetches at most
+ * n_reads - 1 edges instead of the list.  (An id that occurs in self-loops only is in no accepted
+ * edge, so the replay does not return its one-member component; get_connections lists no
+ * self-loop, :316.)  A capped or restricted call has rejections that depend
+ * on sizes and flags, not on connectivity alone; the forest does not answer it.
+ * ------------------------------------------------------------------------------ */
+
+/* Edges: x == NULL and y == NULL: the ctx's current ordered connection result, i.e. what
+ *   hga_connections_fetch_range returns (after hga_connections_run, hga_components_connections or
+ *   hga_connections_gather; n is ignored; HGA_ERR_STATE without one).  Both given: n host pairs of
+ *   ReadIDs, copied.  Exactly one NULL: HGA_ERR_INVALID.  The call works on entries
+ *   [first, first + count), clipped to the list as hga_connections_fetch_range clips; more than
+ *   2^32 - 2 entries after clipping: HGA_ERR_INVALID (positions are 32-bit on the device).
+ * Vertices: the ReadIDs of the current lookup result, [first_read_id, first_read_id + n_reads) (the
+ *   whole input's after hga_lookup_gather).  A given id outside them: HGA_ERR_INVALID with nothing
+ *   launched.  x[i] == y[i] is legal and never accepted.
+ * Result: the positions p, ascending and absolute (first + the place in the range), at which the
+ *   reference loop finds get_parent(x) != get_parent(y); *n_edges (must not be NULL) = their number,
+ *   0 for an empty range.
+ * Synchronous; HGA_ERR_STATE before hga_lookup_run.  The connection result is only read. */
+hga_status hga_spanning_forest(hga_ctx* ctx, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first,
+                               uint64_t count, uint64_t* n_edges);
+/* Copies the last result (caller-allocated, n_edges entries each; any may be NULL): the positions
+ * and the connections' x and y at them.  Valid until the next hga_spanning_forest or hga_lookup_run;
+ * HGA_ERR_STATE before any. */
+hga_status hga_spanning_forest_fetch(hga_ctx* ctx, uint64_t* pos, uint32_t* x, uint32_t* y);
+
+/* ------------------------------------------------------------------------------
  * Measurement: per-kernel device time, recorded with HIP events on the ctx stream.
  * ------------------------------------------------------------------------------ */
 hga_status hga_profile_enable(hga_ctx* ctx, int on);
