@@ -2446,6 +2446,10 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     // ones (the exchange emission needs fb >= 10)
     const uint32_t fb_min = std::getenv("HGA_FB_MIN") ? (uint32_t)std::atoi(std::getenv("HGA_FB_MIN")) : 0u;
     while (fb < fb_max && fb < nbits && ((total_bytes >> fb) > per_bucket || fb < fb_min)) ++fb;
+    // k = 32 never runs without a bucket bit (the hooks included): with fb == 0 the remainder is the whole
+    // 64-bit mixed key, and the one 32-mer that mixes to all ones would equal kc_count<uint64_t>'s EMPTY
+    // (the empty-slot marker and batch padding) and be dropped; a remainder of <= 63 bits cannot
+    if (nbits == 64 && fb == 0) fb = 1;
     kp.fb = fb;
     kp.nb = 1u << fb;
     kp.rbits = nbits - fb;

@@ -124,8 +124,12 @@ def test_count_edge_inputs(gpu_ctx):
 
 @pytest.mark.parametrize("lazy", ["0", "1"])
 def test_count_claim_modes(gpu_ctx, hga_mod, monkeypatch, lazy):
-    """kc_count_s with new keys claimed inline (0) or through the miss queue (1), forced either way
-    (count_run picks by instances per bucket): random, all-distinct (table splits) and heavy inputs."""
+    """HGA_CS_LAZY forces kc_count_s to claim new keys inline (0) or through the miss queue (1) (count_run
+    picks by instances per bucket).  Only the last leg (k = 13, heavy poly-A) reaches kc_count_s here: the
+    k = 19 leg has 75 KB, so fb = 1 and 2k - fb = 37 bits of remainder, and the k = 25 leg ("table splits")
+    has k > 21, so both run the generic kc_count<u64>, which the variable does not touch.  kc_count_s at
+    k = 19 in either claim mode and its sub-range splitting are in test_count_paths_gpu.py
+    (test_headline_variants, test_count_s_subrange_split)."""
     monkeypatch.setenv("HGA_CS_LAZY", lazy)
     streams = random_streams(19, 2, 400, 120, "ACGTACGTACGTNacgt")
     assert_same(run_gpu(gpu_ctx, streams, 19, 2, 6), oracle.count_pipeline(streams, 19, 2, 6))
