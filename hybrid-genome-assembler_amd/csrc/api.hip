@@ -176,6 +176,12 @@ hga_status hga_spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y,
     HGA_CTX_GUARD(c, hga::spanning_forest(c, x, y, n, first, count, n_edges));
 }
 
+hga_status hga_spanning_forest_restricted(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first,
+                                          uint64_t count, const uint32_t* restricted, uint64_t n_restricted,
+                                          uint64_t* n_edges) {
+    HGA_CTX_GUARD(c, hga::spanning_forest_restricted(c, x, y, n, first, count, restricted, n_restricted, n_edges));
+}
+
 hga_status hga_spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uint32_t* y) {
     HGA_CTX_GUARD(c, hga::spanning_forest_fetch(c, pos, x, y));
 }

@@ -1,11 +1,15 @@
-// forest.hip — hga_spanning_forest: the connections union_find accepts
-// (src/clustering/ReadClusteringEngine.cpp:424-489) when it has no size cap and no restricted ids, i.e.
-// the positions p of an ordered connection list at which get_parent(x) != get_parent(y).
+// forest.hip — hga_spanning_forest[_restricted]: the connections union_find accepts
+// (src/clustering/ReadClusteringEngine.cpp:424-489) when it has no size cap, i.e. the positions p of an
+// ordered connection list at which get_parent(x) != get_parent(y) and (with restricted ids, :456) the two
+// components do not both hold one.
 //
-// With an edge's weight its position in the list (all distinct), those edges are the unique minimum
-// spanning forest of the multigraph, so any order of finding them gives the same set.  Borůvka rounds:
+// With an edge's weight its position in the list (all distinct), the edges of the unrestricted call are
+// the unique minimum spanning forest of the multigraph, so any order of finding them gives the same set.
+// The restricted call is the same on the multigraph with all restricted ids contracted into one vertex
+// (hga.h, "Spanning forest"): only the start differs.  Borůvka rounds:
 //
 //   sf_init   comp[v] = v, best[v] = none.
+//   sf_restrict   (restricted call only) comp[r] = R for every restricted vertex r, R the smallest of them.
 //   sf_min    one pass over the live edges (round 0: the range itself).  cx = comp[x], cy = comp[y]; an
 //             edge inside one component is dropped for good, any other is kept for the next round
 //             (compacted through LDS, one cursor add per workgroup) and offered to both components:
@@ -28,6 +32,24 @@
 //   finish    the accepted positions sorted ascending (at most V - 1), x and y gathered at them.
 //
 // One host synchronisation per sf_jump launch, the first of which is the round's own.
+//
+// The contracted start.  After sf_restrict the pointer forest has depth <= 1: R is a root, every other
+// restricted vertex points at it, every other vertex at itself.  That is a state the rounds already meet
+// (it is what a star round leaves once flattened), so the kernels run as they are:
+//   - "offers only ever go to roots": sf_min offers to comp[x] and comp[y], and every round starts flat (each
+//     comp value is a root), the first one now by construction instead of by identity.  A restricted vertex
+//     other than R is never a comp value, so it gets no offer, its best stays none, sf_hook copies its
+//     pointer, and it is never a root again (sf_jump only moves pointers towards roots).
+//   - acc holds at most V - 1: the hooks of all rounds are a forest of the contracted graph, which has
+//     V - (distinct restricted ids) + 1 <= V vertices.
+//   - "live edges but no hook": a live edge joins two roots, so both have a best; the smallest live position
+//     is the best of both its ends, and the end with the larger id hooks.  No word of that depends on the start.
+//   - max_jumps: a pointer path visits distinct vertices, so its depth is at most V - 1 whatever the start, and
+//     ceil(log2 V) + 1 doublings flatten it.
+// An edge between two restricted ids has cx == cy == R in round 0 and is dropped like a self-loop.
+// In the enrichment list (:788-789) nearly every live edge has R on one side, so best[R] is the hot word of
+// round 0: the restricted call relies on sf_offer's read before the atomic and on its one atomic per wave
+// and target, which were written for the star shapes (one word takes ~88 device atomics per µs chip-wide).
 #include "hga_internal.hpp"
 
 namespace hga {
@@ -53,6 +75,15 @@ __global__ void __launch_bounds__(SF_T) sf_init(uint32_t* __restrict__ comp, uin
         best[v] = SF_NIL;
     }
     if (v < SF_WORDS) ctr[v] = 0;
+}
+
+// comp[r - first_id] = R for the n restricted ids (checked on the host; duplicates write the same word twice)
+__global__ void __launch_bounds__(SF_T) sf_restrict(uint32_t* __restrict__ comp, const uint32_t* __restrict__ restricted,
+                                                    uint32_t n, uint32_t first_id, uint32_t V, uint32_t R) {
+    const uint32_t j = blockIdx.x * SF_T + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t v = restricted[j] - first_id;
+    if (v < V) comp[v] = R;
 }
 
 // best[t] = min(best[t], i) for the lanes with want set.  Called by every lane of the wave.
@@ -200,13 +231,13 @@ __global__ void __launch_bounds__(SF_T) sf_gather(const uint32_t* __restrict__ e
     y[j] = ey[e];
 }
 
-}  // namespace
-
-void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n_given, uint64_t first, uint64_t count,
-                     uint64_t* n_edges) {
+// n_restricted == 0: nothing of the restricted call is read or launched
+void spanning_forest_run(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n_given, uint64_t first, uint64_t count,
+                         const uint32_t* restricted, uint64_t n_restricted, uint64_t* n_edges) {
     auto& L = c->lookup;
     auto& F = c->forest;
     HGA_REQUIRE(n_edges, HGA_ERR_INVALID, "null n_edges");
+    HGA_REQUIRE(restricted || n_restricted == 0, HGA_ERR_INVALID, "null restricted list with a count");
     HGA_REQUIRE((x == nullptr) == (y == nullptr), HGA_ERR_INVALID, "exactly one of x and y is null");
     HGA_REQUIRE(L.ran, HGA_ERR_STATE, "hga_lookup_run not called");
     HGA_REQUIRE(x || c->conn.ready, HGA_ERR_STATE, "no connection result: hga_connections_run not called");
@@ -219,6 +250,13 @@ void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t 
         for (uint64_t i = a; i < a + n64; ++i)
             HGA_REQUIRE(x[i] >= first_id && x[i] - first_id < V && y[i] >= first_id && y[i] - first_id < V, HGA_ERR_INVALID,
                         "id outside the lookup's reads");
+    HGA_REQUIRE(n_restricted <= 0xFFFFFFFFull, HGA_ERR_INVALID, "more than 2^32 - 1 restricted ids");
+    uint32_t R = SF_NIL;   // the smallest restricted vertex
+    for (uint64_t i = 0; i < n_restricted; ++i) {
+        HGA_REQUIRE(restricted[i] >= first_id && restricted[i] - first_id < V, HGA_ERR_INVALID,
+                    "restricted id outside the lookup's reads");
+        R = std::min(R, restricted[i] - first_id);
+    }
     F.have = false;
     F.n = 0;
     F.first = a;
@@ -251,6 +289,15 @@ void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t 
     const unsigned vgrid = sf_grid(V, SF_VTILE);
     c->launch("sf_init", [&] { hipLaunchKernelGGL(sf_init, dim3(sf_grid(V, SF_T)), dim3(SF_T), 0, c->stream, comp_a, best, V, ctr); });
     c->check_launch("sf_init");
+    if (n_restricted) {   // the contracted start: every restricted vertex points at R
+        const uint32_t nr = (uint32_t)n_restricted;
+        uint32_t* dr = static_cast<uint32_t*>(F.restricted.ensure((uint64_t)nr * 4));
+        HGA_HIP(hipMemcpyAsync(dr, restricted, (uint64_t)nr * 4, hipMemcpyHostToDevice, c->stream));
+        c->launch("sf_restrict", [&] {
+            hipLaunchKernelGGL(sf_restrict, dim3(sf_grid(nr, SF_T)), dim3(SF_T), 0, c->stream, comp_a, dr, nr, first_id, V, R);
+        });
+        c->check_launch("sf_restrict");
+    }
 
     int max_jumps = 1;   // ceil(log2 V) + 1
     while ((1ull << (max_jumps - 1)) < V) ++max_jumps;
@@ -312,6 +359,19 @@ void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t 
     F.n = accepted;
     F.have = true;
     *n_edges = accepted;
+}
+
+}  // namespace
+
+void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first, uint64_t count,
+                     uint64_t* n_edges) {
+    spanning_forest_run(c, x, y, n, first, count, nullptr, 0, n_edges);
+}
+
+void spanning_forest_restricted(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first,
+                                uint64_t count, const uint32_t* restricted, uint64_t n_restricted, uint64_t* n_edges) {
+    c->forest.have = false;   // a failed call leaves no result to fetch
+    spanning_forest_run(c, x, y, n, first, count, restricted, n_restricted, n_edges);
 }
 
 void spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uint32_t* y) {

@@ -250,6 +250,7 @@ struct ForestState {
     bool have = false;
     uint64_t n = 0, first = 0;
     DevBuf ex, ey, comp_a, comp_b, best, live_a, live_b, acc, ctr, sort, pos, x, y;
+    DevBuf restricted;   // hga_spanning_forest_restricted's uploaded id list
 };
 
 // Multi-GPU transport of one rank (comm.hip): RCCL over xGMI, or a caller's host-staged hook.
@@ -383,9 +384,11 @@ void components_overlaps_device(hga_ctx* c, const uint32_t* dx, const uint32_t* 
 void tree_tails(hga_ctx* c, const uint64_t* tree_ptr, const uint32_t* ex, const uint32_t* ey, uint64_t n_trees,
                 const int32_t* overlap, const uint32_t* read_length, uint64_t tail_length, uint64_t* left_ptr,
                 uint32_t* left, uint64_t* right_ptr, uint32_t* right, hga_tree_ends* ends);
-// forest.hip: the connections an uncapped, unrestricted union_find accepts (hga_spanning_forest*)
+// forest.hip: the connections an uncapped union_find accepts, without and with restricted ids (hga_spanning_forest*)
 void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first, uint64_t count,
                      uint64_t* n_edges);
+void spanning_forest_restricted(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first,
+                                uint64_t count, const uint32_t* restricted, uint64_t n_restricted, uint64_t* n_edges);
 void spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uint32_t* y);
 void components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                            const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,

@@ -109,6 +109,8 @@ HGA_SYMBOLS = {
     "hga_tree_tails": (C.c_int, [_vp, _u64p, _u32p, _u32p, C.c_uint64, _i32p, _u32p, C.c_uint64, _u64p, _u32p, _u64p,
                                  _u32p, C.POINTER(TreeEnds)]),
     "hga_spanning_forest": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint64, _u64p]),
+    "hga_spanning_forest_restricted": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint64, _u32p, C.c_uint64,
+                                                 _u64p]),
     "hga_spanning_forest_fetch": (C.c_int, [_vp, _u64p, _u32p, _u32p]),
     "hga_components_get_sizes": (C.c_int, [_vp, C.POINTER(ComponentsSizes)]),
     "hga_components_fetch_index": (C.c_int, [_vp, _u64p, _u32p]),
@@ -543,11 +545,13 @@ class Ctx:
                 [right[int(rp[t]):int(rp[t + 1])].copy() for t in range(nt)],
                 [(e.right_id, e.right_dist, e.left_id, e.left_dist) for e in ends[:nt]])
 
-    # ---- spanning forest (the connections an uncapped, unrestricted union_find accepts)
-    def spanning_forest(self, x=None, y=None, first: int = 0, count=None):
+    # ---- spanning forest (the connections an uncapped union_find accepts)
+    def spanning_forest(self, x=None, y=None, first: int = 0, count=None, restricted=None):
         """(pos uint64[m], x uint32[m], y uint32[m]): the ascending positions in [first, first + count)
         (clipped; count None: to the end) at which union_find joins two components, and the connections
-        there.  x, y: ReadID arrays, or both None for the ctx's current ordered connection result."""
+        there.  x, y: ReadID arrays, or both None for the ctx's current ordered connection result.
+        restricted: ReadIDs of which no two may end in one component (union_find's restricted set), through
+        hga_spanning_forest_restricted; None: hga_spanning_forest."""
         if (x is None) != (y is None):
             raise ValueError("x and y must both be given or both be None")
         xv = yv = None
@@ -556,9 +560,13 @@ class Ctx:
             if xv.shape != yv.shape or xv.ndim != 1:
                 raise ValueError("x and y must be one-dimensional and of equal length")
         m = C.c_uint64()
-        _ck(lib().hga_spanning_forest(self._h, None if xv is None else _p(xv, C.c_uint32),
-                                      None if yv is None else _p(yv, C.c_uint32), 0 if xv is None else len(xv), first,
-                                      2 ** 64 - 1 if count is None else count, C.byref(m)))
+        edges = (self._h, None if xv is None else _p(xv, C.c_uint32), None if yv is None else _p(yv, C.c_uint32),
+                 0 if xv is None else len(xv), first, 2 ** 64 - 1 if count is None else count)
+        if restricted is None:
+            _ck(lib().hga_spanning_forest(*edges, C.byref(m)))
+        else:
+            rv = np.ascontiguousarray(restricted, np.uint32).ravel()
+            _ck(lib().hga_spanning_forest_restricted(*edges, _p(rv, C.c_uint32) if len(rv) else None, len(rv), C.byref(m)))
         pos, ox, oy = np.zeros(m.value, np.uint64), np.zeros(m.value, np.uint32), np.zeros(m.value, np.uint32)
         _ck(lib().hga_spanning_forest_fetch(self._h, _p(pos, C.c_uint64), _p(ox, C.c_uint32), _p(oy, C.c_uint32)))
         return pos, ox, oy
@@ -785,6 +793,7 @@ CLUSTER_SYMBOLS = {
                                       _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32, C.POINTER(ClusterConfig), C.c_int,
                                       C.POINTER(_u32p), _u64p, C.POINTER(_u32p), C.POINTER(_vp), C.c_int, _u64p]),
     "hgc_forest_calls": (C.c_uint64, []),
+    "hgc_enrich_forest_calls": (C.c_uint64, []),
     "hgc_union_find": (C.c_int, [_u32p, _u32p, _u64p, C.c_uint64, _u32p, C.c_uint64, C.c_int, C.c_int,
                                  C.POINTER(_u64p), C.POINTER(_u32p), _u64p, C.POINTER(_u64p), C.POINTER(_u32p)]),
     "hgc_spectral": (C.c_int, [_u32p, _u32p, _u64p, C.c_uint64, C.c_int, C.POINTER(_u64p), C.POINTER(_u32p), _u64p]),
@@ -858,7 +867,7 @@ def sym_eigen(a):
 
 def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None, debug=False, first_read_id=1,
                  start=None, end=None, batched_overlaps=False, stats=None, device_sets=False, device_tails=False,
-                 device_forest=False):
+                 device_forest=False, device_enrich=False):
     """run_clustering after construct_indices on the host (no device state): (component ids,
     per-read component id (0 = none), log text).  start / end: the reads' simulator coordinates
     (print_components' intervals under debug), None = 0.
@@ -872,7 +881,10 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
     HGA_DEVICE_TAILS=1), bound to the engine's host implementation.
     device_forest: the first union_find replays only the connections it would accept, taken from the
     spanning-forest hook (the path of HGA_DEVICE_FOREST=1), bound to the engine's host implementation;
-    stats then also receives "forest_calls"."""
+    stats then also receives "forest_calls".
+    device_enrich: the enrichment union_find replays only the connections it would accept, taken from the
+    enrichment-forest hook (the path of HGA_DEVICE_ENRICH=1), bound to the engine's host implementation;
+    stats then also receives "enrich_forest_calls"."""
     L = cluster_lib()
     cfg = cfg or cluster_config()
     off = np.ascontiguousarray(offsets, np.uint64)
@@ -894,12 +906,14 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
                                _p(a["kci_read"], C.c_uint32), len(a["kci_ptr"]) - 1, C.byref(cfg), 1 if debug else 0,
                                C.byref(ip), C.byref(ni), C.byref(op), C.byref(lp),
                                (1 if batched_overlaps else 0) | (2 if device_sets else 0) | (4 if device_tails else 0) |
-                               (8 if device_forest else 0),
+                               (8 if device_forest else 0) | (16 if device_enrich else 0),
                                _p(ove, C.c_uint64)))
     if stats is not None:
         stats["overlap_edges_batched"], stats["overlap_edges_host"] = int(ove[0]), int(ove[1])
         if device_forest:
             stats["forest_calls"] = int(L.hgc_forest_calls())
+        if device_enrich:
+            stats["enrich_forest_calls"] = int(L.hgc_enrich_forest_calls())
     ids = _take(ip, ni.value, np.uint32, L.hgc_free)
     owner = _take(op, n, np.uint32, L.hgc_free)
     log = C.string_at(lp.value).decode()

@@ -13,6 +13,7 @@
 namespace {
 thread_local std::string g_err;
 thread_local uint64_t g_forest_calls = 0;   // of this thread's last hgc_cluster* call (hgc_forest_calls)
+thread_local uint64_t g_enrich_calls = 0;   // likewise (hgc_enrich_forest_calls)
 
 template <class F>
 int guard(F&& f) {
@@ -82,7 +83,10 @@ void hgc_free(void* p) { std::free(p); }
 // tails of all trees from one call, as under HGA_DEVICE_TAILS=1;
 // 8 sets the spanning-forest hook (set_device_forest) to host_forest, so that the first union_find replays
 // only the connections it would accept, as under HGA_DEVICE_FOREST=1; hgc_forest_calls() then tells how
-// many times this thread's last hgc_cluster* call took that path.
+// many times this thread's last hgc_cluster* call took that path;
+// 16 sets the enrichment-forest hook (set_device_enrich_forest) to host_enrich_forest, so that the
+// enrichment union_find replays only the connections it would accept, as under HGA_DEVICE_ENRICH=1;
+// hgc_enrich_forest_calls() then tells how many times this thread's last hgc_cluster* call took that path.
 int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
                 const uint32_t* end, uint64_t n_reads,
                 uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
@@ -135,10 +139,15 @@ int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_
             e.set_device_forest([&e](hgah::Score min_score, uint32_t min_kmers, double keep_fraction) {
                 return e.host_forest(min_score, min_kmers, keep_fraction);
             });
+        if (batched & 16)
+            e.set_device_enrich_forest([&e](const std::vector<hgah::ComponentID>& pivots, hgah::Score min_score) {
+                return e.host_enrich_forest(pivots, min_score);
+            });
         std::ostringstream log;
-        g_forest_calls = 0;
+        g_forest_calls = g_enrich_calls = 0;
         const auto ids = e.run(log);
         g_forest_calls = e.forest_calls();
+        g_enrich_calls = e.enrich_forest_calls();
         if (ov_edges) {
             ov_edges[0] = e.overlap_edges_device();
             ov_edges[1] = e.overlap_edges_host();
@@ -166,6 +175,7 @@ int hgc_cluster(const char* bases, const uint64_t* offsets, const int32_t* categ
 }
 
 uint64_t hgc_forest_calls(void) { return g_forest_calls; }
+uint64_t hgc_enrich_forest_calls(void) { return g_enrich_calls; }
 
 // union_find (ReadClusteringEngine.cpp:424-489) of an ordered connection list.
 int hgc_union_find(const uint32_t* x, const uint32_t* y, const uint64_t* s, uint64_t n, const uint32_t* restricted,

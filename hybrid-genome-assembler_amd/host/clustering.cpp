@@ -533,6 +533,7 @@ ClusteringEngine::ClusteringEngine(const ClusteringConfig& cfg, bool debug, cons
     dev_sets_ = dev_comp_ && device_sets_requested();   // the KmerID lists stay on the device
     dev_tails_ = dev_sets_ && device_tails_requested();
     dev_forest_ = dev_comp_ && device_forest_requested();
+    dev_enrich_ = dev_comp_ && device_enrich_requested();
     if (dev_tails_) {
         read_len_.resize(n);
         for (uint64_t i = 0; i < n; ++i) read_len_[i] = (uint32_t)(reads.offsets[i + 1] - reads.offsets[i]);
@@ -606,6 +607,18 @@ bool ClusteringEngine::forest_applies() const {
     return pristine_ && cfg_.scaffold_forming_score == 0 && cfg_.scaffold_component_max_size == -1 &&
            (dev_forest_fn_ || (dev_forest_ && !dev_conn_));
 }
+
+bool ClusteringEngine::device_enrich_requested() {
+    auto on = [](const char* name) {
+        const char* v = std::getenv(name);
+        return v && std::string(v) == "1";
+    };
+    return on("HGA_DEVICE_ENRICH") && !on("HGA_HOST_CONNECTIONS");
+}
+
+// The enrichment union_find (see clustering.h): the hook, else the merged component state on the ctx, which
+// get_connections would read (after the merges only gpu_ holds the state, with --gpus N too).
+bool ClusteringEngine::enrich_forest_applies() const { return dev_enrich_fn_ || (dev_enrich_ && !pristine_ && dev_comp_); }
 
 bool ClusteringEngine::sets_mode() const { return dev_sets_ || (dev_cov_ && dev_sets_fn_); }
 
@@ -770,6 +783,60 @@ ClusteringEngine::ForestEdges ClusteringEngine::host_forest(Score min_score, uin
         const ComponentID px = root(c.x), py = root(c.y);
         if (px == py) continue;
         parent[px] = py;
+        out.edges.emplace_back(c.x, c.y);
+    }
+    return out;
+}
+
+// get_connections' merged-state branch without the fetch: the list stays on the device and only the
+// connections union_find(…, restricted = pivots, 2, -1) would accept come back.
+ClusteringEngine::ForestEdges ClusteringEngine::device_enrich_forest(const std::vector<ComponentID>& pivots,
+                                                                     Score min_score) {
+    std::vector<ComponentID> piv;
+    for (ComponentID p : pivots)
+        if (index_.count(p)) piv.push_back(p);   // (host_connections skips the others)
+    uint64_t n = 0;
+    if (hga_components_connections(gpu_, piv.data(), piv.size(), min_score, &n) != HGA_OK)
+        throw std::runtime_error(std::string("hga_components_connections: ") + hga_last_error());
+    ++conn_dev_calls_;
+    uint64_t e = 0;
+    if (hga_spanning_forest_restricted(gpu_, nullptr, nullptr, 0, 0, n, pivots.data(), pivots.size(), &e) != HGA_OK)
+        throw std::runtime_error(std::string("hga_spanning_forest_restricted: ") + hga_last_error());
+    std::vector<uint32_t> x(e), y(e);
+    if (hga_spanning_forest_fetch(gpu_, nullptr, x.data(), y.data()) != HGA_OK)
+        throw std::runtime_error(std::string("hga_spanning_forest_fetch: ") + hga_last_error());
+    ForestEdges out;
+    out.connections = n;
+    out.edges.resize(e);
+    for (uint64_t i = 0; i < e; ++i) out.edges[i] = {x[i], y[i]};
+    return out;
+}
+
+ClusteringEngine::ForestEdges ClusteringEngine::host_enrich_forest(const std::vector<ComponentID>& pivots,
+                                                                   Score min_score) {
+    const std::vector<Connection> conns = get_connections(pivots, min_score);
+    const std::set<ComponentID> restricted(pivots.begin(), pivots.end());
+    ForestEdges out;
+    out.connections = conns.size();
+    std::unordered_map<ComponentID, ComponentID> parent;
+    std::unordered_map<ComponentID, bool> holds;   // per root: the component holds a restricted id
+    auto root = [&](ComponentID v) {
+        if (parent.emplace(v, v).second) holds[v] = restricted.count(v) != 0;
+        ComponentID r = v;
+        while (parent[r] != r) r = parent[r];
+        while (parent[v] != r) {
+            const ComponentID nx = parent[v];
+            parent[v] = r;
+            v = nx;
+        }
+        return r;
+    };
+    for (const Connection& c : conns) {
+        const ComponentID px = root(c.x), py = root(c.y);
+        if (px == py) continue;
+        if (holds[px] && holds[py]) continue;
+        parent[px] = py;
+        holds[py] = holds[py] || holds[px];
         out.edges.emplace_back(c.x, c.y);
     }
     return out;
@@ -1544,8 +1611,23 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
     auto core_ids = component_ids(min_size);
     print_components(core_ids, out);   // :781 (sorts core_ids in place, as there)
     {   // :785-794
-        conns = timed(out, "Calculation of enrichment connections",
-                      [&] { return get_connections(core_ids, cfg_.enrichment_connections_min_score); });
+        if (enrich_forest_applies()) {
+            // the list stays on the device: only the connections union_find accepts come back, in position
+            // order, and its replay over them with the same restricted set repeats the full list's merges
+            const ForestEdges fe = timed(out, "Calculation of enrichment connections", [&] {
+                const Score s = cfg_.enrichment_connections_min_score;
+                return dev_enrich_fn_ ? dev_enrich_fn_(core_ids, s) : device_enrich_forest(core_ids, s);
+            });
+            ++enrich_calls_;
+            enrich_conns_ = fe.connections;
+            enrich_edges_ = fe.edges.size();
+            conns.clear();
+            conns.reserve(fe.edges.size());
+            for (auto& e : fe.edges) conns.push_back({e.first, e.second, 0, false});
+        } else {
+            conns = timed(out, "Calculation of enrichment connections",
+                          [&] { return get_connections(core_ids, cfg_.enrichment_connections_min_score); });
+        }
         restricted.insert(core_ids.begin(), core_ids.end());
         comps_and_trees = union_find(conns, restricted, 2, -1);
         timed(out, "Merging into core components", [&] { return merge_components(extract_components(comps_and_trees)); });
@@ -1560,6 +1642,10 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
         std::fprintf(stderr, "hga-timing forest.device_calls %llu\nhga-timing forest.connections %llu\nhga-timing forest.edges %llu\n",
                      (unsigned long long)forest_calls_, (unsigned long long)forest_conns_,
                      (unsigned long long)forest_edges_);
+    if (const char* te = std::getenv("HGA_TIMING"); enrich_calls_ && te && std::string(te) == "1")
+        std::fprintf(stderr, "hga-timing enrich.device_calls %llu\nhga-timing enrich.connections %llu\nhga-timing enrich.edges %llu\n",
+                     (unsigned long long)enrich_calls_, (unsigned long long)enrich_conns_,
+                     (unsigned long long)enrich_edges_);
     return core_ids;
 }
 

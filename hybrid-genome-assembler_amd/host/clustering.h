@@ -203,7 +203,7 @@ class ClusteringEngine {
     // fn(min_score, min_kmers, keep_fraction) -> the accepted (x, y) in position order and the prefix length.
     struct ForestEdges {
         SpanningTree edges;
-        uint64_t connections = 0;   // the scaffold-forming prefix they were taken from
+        uint64_t connections = 0;   // the length of the list they were taken from (the scaffold-forming prefix; the enrichment list)
     };
     using DeviceForest = std::function<ForestEdges(Score min_score, uint32_t min_kmers, double keep_fraction)>;
     void set_device_forest(DeviceForest fn) { dev_forest_fn_ = std::move(fn); }
@@ -213,9 +213,30 @@ class ClusteringEngine {
     // HGA_DEVICE_FOREST=1 without HGA_HOST_CONNECTIONS=1: what an engine with a ctx runs.
     static bool device_forest_requested();
     uint64_t forest_calls() const { return forest_calls_; }
+    // The enrichment union_find (:785-794) from a restricted spanning forest (HGA_DEVICE_ENRICH=1, opt-in).
+    // union_find(conns, restricted = core ids, 2, -1) also rejects a connection whose two components both
+    // hold a restricted id (:456); with all restricted ids contracted into one vertex that is again the
+    // minimum spanning forest of the list (hga.h, "Spanning forest"), and the replay over the accepted
+    // connections with the same restricted set repeats the full list's merges.  When the step would read
+    // the device's component state (merges done, no HGA_HOST_CONNECTIONS=1) run() leaves
+    // hga_components_connections' list on the device, has hga_spanning_forest_restricted find the
+    // accepted connections and fetches only those; a pristine engine, one without a ctx and one with only
+    // a connection hook run the step as before.
+    // fn(pivots = the core ids, also the restricted set; min_score) -> the accepted (x, y) in position
+    // order and the length of the enrichment list.
+    using DeviceEnrichForest = std::function<ForestEdges(const std::vector<ComponentID>& pivots, Score min_score)>;
+    void set_device_enrich_forest(DeviceEnrichForest fn) { dev_enrich_fn_ = std::move(fn); }
+    // The hook's semantics on the host (the hook of the device-less tests): get_connections' list, then the
+    // loop's two rejection rules.
+    ForestEdges host_enrich_forest(const std::vector<ComponentID>& pivots, Score min_score);
+    // HGA_DEVICE_ENRICH=1 without HGA_HOST_CONNECTIONS=1: what an engine with a ctx runs.
+    static bool device_enrich_requested();
+    uint64_t enrich_forest_calls() const { return enrich_calls_; }
 
    private:
     bool forest_applies() const;
+    bool enrich_forest_applies() const;
+    ForestEdges device_enrich_forest(const std::vector<ComponentID>& pivots, Score min_score);
     ForestEdges device_forest(Score min_score, uint32_t min_kmers, double keep_fraction);
     // hga_connections_run of the pristine state as get_connections calls it; returns the list's length
     uint64_t device_connections_run(const std::vector<ComponentID>& pivots, Score min_score, uint32_t min_kmers);
@@ -260,6 +281,9 @@ class ClusteringEngine {
     DeviceForest dev_forest_fn_;
     bool dev_forest_ = false;   // HGA_DEVICE_FOREST=1 with the component state on the device
     uint64_t forest_calls_ = 0, forest_conns_ = 0, forest_edges_ = 0;
+    DeviceEnrichForest dev_enrich_fn_;
+    bool dev_enrich_ = false;   // HGA_DEVICE_ENRICH=1 with the component state on the device
+    uint64_t enrich_calls_ = 0, enrich_conns_ = 0, enrich_edges_ = 0;
     uint64_t ov_edges_dev_ = 0, ov_edges_host_ = 0;
     bool pristine_ = true;   // no merge yet: the device indices still describe the state
     int gpu_calls_ = 0;

@@ -468,8 +468,27 @@ hga_status hga_components_reset(hga_ctx* ctx);
  * SpanningTree edge order and the order of the result are the same, and a caller fetches at most
  * n_reads - 1 edges instead of the list.  (An id that occurs in self-loops only is in no accepted
  * edge, so the replay does not return its one-member component; get_connections lists no
- * self-loop, :316.)  A capped or restricted call has rejections that depend
- * on sizes and flags, not on connectivity alone; the forest does not answer it.
+ * self-loop, :316.)
+ * Restricted ids (hga_spanning_forest_restricted): with max_component_size = -1 the loop also
+ * rejects a connection whose two components both hold a restricted id (:456; the flag of a merged
+ * component is the OR of its parts, :478).  That is still a spanning forest: contract all
+ * restricted ids into one vertex R.  By induction over the list the components of the contracted
+ * graph are the original ones with all restricted-holding components fused into R's.  A
+ * connection inside one original component is inside one contracted component; a connection
+ * between two restricted-holding components is inside R's component; any other connection joins
+ * two distinct components in both graphs, and accepting it merges the corresponding components
+ * in both.  So the accepted positions are those of the plain loop on the contracted multigraph,
+ * its unique minimum spanning forest with the position as weight, and the device runs the same
+ * rounds from a start in which every restricted id already points at R.  A connection between
+ * two restricted ids is a self-loop there and is never accepted.  The replay carries over
+ * unchanged: union_find(accepted connections, restricted, min, -1) repeats the merges of the
+ * full list, every other connection having changed nothing.  What the replay does not return is
+ * again the one-member component of an id with no accepted connection, now also a restricted id
+ * that only ever meets restricted-holding components; the enrichment step, the one restricted
+ * call of run_clustering (:788-789), asks for components of at least 2.
+ * Only a size-capped call (max_component_size != -1) is not answered: whether it rejects a
+ * connection depends on component sizes, so its accepted sets are not the independent sets of
+ * a matroid and the order of finding them matters.
  * ------------------------------------------------------------------------------ */
 
 /* Edges: x == NULL and y == NULL: the ctx's current ordered connection result, i.e. what
@@ -487,9 +506,22 @@ hga_status hga_components_reset(hga_ctx* ctx);
  * Synchronous; HGA_ERR_STATE before hga_lookup_run.  The connection result is only read. */
 hga_status hga_spanning_forest(hga_ctx* ctx, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first,
                                uint64_t count, uint64_t* n_edges);
+/* hga_spanning_forest with restricted ids.  Edges, range, clipping, vertices, state rules and
+ * synchrony as there; the result is fetched with hga_spanning_forest_fetch.
+ * restricted: n_restricted ReadIDs in host memory, copied; duplicates, ids that occur in no edge
+ *   and ids without hits are legal.  An id outside the lookup's reads: HGA_ERR_INVALID with nothing
+ *   launched.  NULL with n_restricted > 0: HGA_ERR_INVALID.  n_restricted == 0: the call is
+ *   hga_spanning_forest (restricted is not read).
+ * Result: the positions p, ascending and absolute, at which the reference loop finds two different
+ *   parents that do not both hold a restricted id.
+ * A failed call leaves no result: hga_spanning_forest_fetch returns HGA_ERR_STATE until the next
+ * call that succeeds. */
+hga_status hga_spanning_forest_restricted(hga_ctx* ctx, const uint32_t* x, const uint32_t* y, uint64_t n,
+                                          uint64_t first, uint64_t count, const uint32_t* restricted,
+                                          uint64_t n_restricted, uint64_t* n_edges);
 /* Copies the last result (caller-allocated, n_edges entries each; any may be NULL): the positions
- * and the connections' x and y at them.  Valid until the next hga_spanning_forest or hga_lookup_run;
- * HGA_ERR_STATE before any. */
+ * and the connections' x and y at them.  Valid until the next hga_spanning_forest[_restricted] or
+ * hga_lookup_run; HGA_ERR_STATE before any. */
 hga_status hga_spanning_forest_fetch(hga_ctx* ctx, uint64_t* pos, uint32_t* x, uint32_t* y);
 
 /* ------------------------------------------------------------------------------
