@@ -2513,7 +2513,9 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     const uint32_t slot_b = (uint32_t)esz + 4u * F;
     uint32_t T = 1;
     while ((uint64_t)T * 2 * slot_b <= LDS_TAB) T *= 2;
-    HGA_REQUIRE(T >= 2 * NT_C, HGA_ERR_INVALID, "too many files for the LDS table");
+    // (a slot holds one counter per file: 14 files with u64 remainders, 15 with u32 ones.  A session whose
+    // files all come from dump rows counts nothing, its empty buckets never fill a slot: any T will do)
+    HGA_REQUIRE(T >= 2 * NT_C || total_bytes == 0, HGA_ERR_INVALID, "too many files with reads for the LDS table");
     const uint32_t maxload = std::min<uint32_t>((uint32_t)(T * 0.85), T - NT_C - 8);
     void* binned = s.binned.ensure(std::max<size_t>(total_bytes, 1) * esz);
 

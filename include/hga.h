@@ -52,9 +52,13 @@ hga_status hga_ctx_destroy(hga_ctx* ctx);
  *   get_specificity, export_kmers; src/occurrences/JellyfishOccurrenceReader.cpp:63-135).
  * ------------------------------------------------------------------------------ */
 
-/* Starts a counting session: k in [1,32], n_files >= 1 (one file = one haplotype,
+/* Starts a counting session: k in [1,32], n_files in [1,64] (one file = one haplotype,
  * README.md:36).  Replaces JellyfishOccurrenceReader(paths, k)
- * (src/occurrences/JellyfishOccurrenceReader.h:32). */
+ * (src/occurrences/JellyfishOccurrenceReader.h:32).
+ * Reads (hga_count_add) are counted with one counter per file in every slot of the count kernel's
+ * table, which holds up to 14 files (15 when the key bits below the bucket bits number at most 31);
+ * with more files hga_count_run returns HGA_ERR_INVALID unless every file comes from dump rows
+ * (hga_count_add_rows), which are merged without that table. */
 hga_status hga_count_begin(hga_ctx* ctx, int k, uint32_t n_files);
 
 /* Appends sequence bytes of file `file` (copied to HBM).  `seq` holds whole reads

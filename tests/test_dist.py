@@ -63,15 +63,20 @@ def _free_port():
     return p
 
 
-def make_streams(seed=7, n_reads=600, L=3000, heavy=False):
+def make_streams(seed=7, n_reads=600, L=3000, heavy=False, n_files=2):
+    """One read stream per file: file 0 from a random genome, file f > 0 from a copy of it with every 37th
+    base changed (starting at base 5 (f - 1) mod 37, to the letter 1 + (f - 1) mod 3 places on).  The
+    default is the pair of files most tests use; the first two streams do not depend on n_files."""
     rng = random.Random(seed)
     g = "".join(rng.choice("ACGT") for _ in range(L))
-    h = list(g)
-    for i in range(0, L, 37):
-        h[i] = "ACGT"[("ACGT".index(h[i]) + 1) % 4]
-    h = "".join(h)
+    srcs = [g]
+    for f in range(1, n_files):
+        h = list(g)
+        for i in range(5 * (f - 1) % 37, L, 37):
+            h[i] = "ACGT"[("ACGT".index(h[i]) + 1 + (f - 1) % 3) % 4]
+        srcs.append("".join(h))
     out = []
-    for src in (g, h):
+    for src in srcs:
         reads = []
         for _ in range(n_reads):
             s = rng.randrange(0, L - 60)

@@ -18,6 +18,7 @@ import torch
 import hga
 import hga_dist
 import oracle
+import rows_ref
 from test_dist import make_streams
 
 THR = oracle.THRESHOLDS
@@ -93,7 +94,7 @@ def test_partition_merge_min_counts_and_empty_owner():
     assert np.array_equal(keys, rk) and np.array_equal(counts, rc)
 
 
-def _worker(rank, world, port, out_path, k, envs=None, big=False, root=-1):
+def _worker(rank, world, port, out_path, k, envs=None, big=False, root=-1, n_files=2):
     import os
     import torch.distributed as dist
     if envs:   # this rank's exchange test hooks (count.hip / exchange.hip)
@@ -101,7 +102,7 @@ def _worker(rank, world, port, out_path, k, envs=None, big=False, root=-1):
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     ctx = hga.Ctx(0)
     try:
-        streams = make_streams(seed=3, n_reads=100000, L=1500000) if big else make_streams()
+        streams = make_streams(seed=3, n_reads=100000, L=1500000) if big else make_streams(n_files=n_files)
         ctx.count_begin(k, len(streams))
         for f, s in enumerate(streams):
             ctx.count_add(f, hga_dist.shard_reads(s, rank, world))
@@ -155,6 +156,11 @@ def test_count_exchange_processes(tmp_path, monkeypatch, world, k, envs, big, on
     out = str(tmp_path / "d")
     mp.start_processes(_worker, args=(world, port, out, k, envs, big), nprocs=world, start_method="spawn")
     streams = make_streams(seed=3, n_reads=100000, L=1500000) if big else make_streams()
+    _assert_ranks_equal_oracle(out, world, streams, k)
+
+
+def _assert_ranks_equal_oracle(out, world, streams, k):
+    """Every rank's saved answers (_worker) against the single-process oracle over all reads."""
     ref = oracle.count_pipeline(streams, k, 3, 40)
     inst = sum(oracle.count_instances(x, k) for x in streams)
     for rank in range(world):
@@ -166,6 +172,27 @@ def test_count_exchange_processes(tmp_path, monkeypatch, world, k, envs, big, on
         assert np.array_equal(r["rk"], ref["keys"]) and np.array_equal(r["rc"], ref["counts"])
         assert np.array_equal(r["d0k"], ref["dumps"][0][0]) and np.array_equal(r["d0c"], ref["dumps"][0][1])
         assert int(r["inst"]) == inst and int(r["rows"]) == len(ref["keys"])
+    return ref
+
+
+@pytest.mark.parametrize("world,k,F", [(2, 31, 2), (3, 19, 3), (2, 13, 8)])
+def test_count_exchange_processes_file_counts(tmp_path, world, k, F):
+    """The exchange beyond two packable files, in processes over the host transport: (31, 2) does not pack
+    ((64 - 62) / 2 = 1 bit per count), so the rows travel wide to code-range owners (kx_owner_hist /
+    kx_scatter, two all-to-alls, kx_merge_flags / kx_merge_emit) and the export is re-partitioned after
+    that; (19, 3) and (13, 8) pack at 8 and 4 bits per count and are merged by the FMAX = 4 and FMAX = 8
+    instances of kx_xb_merge."""
+    import torch.multiprocessing as mp
+    from test_dist import _free_port
+    assert (rows_ref.pack_bits(k, F) == 0) == (k == 31)
+    out = str(tmp_path / "d")
+    mp.start_processes(_worker, args=(world, _free_port(), out, k, None, False, -1, F), nprocs=world,
+                       start_method="spawn")
+    streams = make_streams(n_files=F)
+    ref = _assert_ranks_equal_oracle(out, world, streams, k)
+    assert ref["counts"].shape[1] == F and len(ref["selected"]) > 100
+    if F > 2:   # rows that only a file past the first two holds reach the owners and the export
+        assert (((ref["counts"] > 0).sum(axis=1) == 1) & (ref["counts"][:, 2:] > 0).any(axis=1)).any()
 
 
 def _sim_packed(streams, k, G, min_c):
