@@ -186,6 +186,15 @@ hga_status hga_spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uin
     HGA_CTX_GUARD(c, hga::spanning_forest_fetch(c, pos, x, y));
 }
 
+hga_status hga_connections_quality(hga_ctx* c, const uint32_t* x, const uint32_t* y, const uint64_t* score,
+                                   const uint8_t* is_good, uint64_t n, int per_candidate, const int32_t* vertex_class,
+                                   uint64_t** out_score, uint64_t** out_good, uint64_t** out_bad, uint64_t* n_rows) {
+    HGA_CTX_GUARD(c, hga::connections_quality(c, x, y, score, is_good, n, per_candidate, vertex_class, out_score, out_good,
+                                              out_bad, n_rows));
+}
+
+uint32_t hga_connections_quality_tile(void) { return hga::connections_quality_tile(); }
+
 hga_status hga_components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                                      const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
                                      uint64_t* set_size) {

@@ -253,6 +253,12 @@ struct ForestState {
     DevBuf restricted;   // hga_spanning_forest_restricted's uploaded id list
 };
 
+// hga_connections_quality's buffers (quality.hip): the uploaded list and classes, the smallest position per
+// vertex, the per-tile counts and the runs; grow-only, reused across calls
+struct QualityState {
+    DevBuf ex, ey, es, eg, vc, first, cnt, rs, rk, rg;
+};
+
 // Multi-GPU transport of one rank (comm.hip): RCCL over xGMI, or a caller's host-staged hook.
 struct Comm {
     int rank = 0, nranks = 1;
@@ -296,6 +302,7 @@ struct hga_ctx {
     hga::ComponentState comp;
     hga::TailsState tails;
     hga::ForestState forest;
+    hga::QualityState quality;
     hga::PinnedBuf pinned;   // small host<->device staging (see count_spec_hist)
     hga::PinnedBuf pinned_sel;   // count_select counters + top-digit histogram
     std::unique_ptr<hga::Comm> comm;   // hga_comm_init*: the count results become global
@@ -390,6 +397,11 @@ void spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t 
 void spanning_forest_restricted(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first,
                                 uint64_t count, const uint32_t* restricted, uint64_t n_restricted, uint64_t* n_edges);
 void spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uint32_t* y);
+// quality.hip: plot_connection_quality's histograms of an ordered connection list (hga_connections_quality)
+void connections_quality(hga_ctx* c, const uint32_t* x, const uint32_t* y, const uint64_t* score, const uint8_t* is_good,
+                         uint64_t n, int per_candidate, const int32_t* vertex_class, uint64_t** out_score,
+                         uint64_t** out_good, uint64_t** out_bad, uint64_t* n_rows);
+uint32_t connections_quality_tile();
 void components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                            const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
                            uint64_t* set_size);

@@ -65,6 +65,9 @@ class Transport(C.Structure):
     _fields_ = [("user", C.c_void_p), ("alltoallv", ALLTOALLV_FN)]
 
 
+# rows per workgroup of hga_connections_quality's kernels (hga_connections_quality_tile)
+QUALITY_TILE = 2048
+
 _lib = None
 _host = None
 
@@ -101,6 +104,9 @@ HGA_SYMBOLS = {
     "hga_connections_run": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint32, C.c_uint64, _i32p, _u64p]),
     "hga_connections_fetch": (C.c_int, [_vp, _u32p, _u32p, _u64p, _u8p]),
     "hga_connections_fetch_range": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p, _u32p, _u64p, _u8p]),
+    "hga_connections_quality": (C.c_int, [_vp, _u32p, _u32p, _u64p, _u8p, C.c_uint64, C.c_int, _i32p, C.POINTER(_u64p),
+                                          C.POINTER(_u64p), C.POINTER(_u64p), _u64p]),
+    "hga_connections_quality_tile": (C.c_uint32, []),
     "hga_read_overlaps": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _i32p, _u32p]),
     "hga_components_merge": (C.c_int, [_vp, _u64p, _u32p, C.c_uint64]),
     "hga_components_connections": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint64, _u64p]),
@@ -466,6 +472,34 @@ class Ctx:
                                               _p(sc, C.c_uint64), _p(g, C.c_uint8)))
         return x, y, sc, g
 
+    # ---- connection quality (plot_connection_quality's histograms of an ordered list)
+    def connections_quality(self, x=None, y=None, score=None, is_good=None, per_candidate: bool = False,
+                            vertex_class=None):
+        """(score uint64[r] ascending, good uint64[r], bad uint64[r]): per distinct score the counted
+        connections that are good / bad.  x, y, score all None: the ctx's current ordered connection
+        result; all given: rows in result order (score non-increasing), is_good None = all 0.
+        per_candidate: one count per distinct y, from its row of the smallest position.  vertex_class:
+        one int per read of the lookup; good = class[x] == class[y] then replaces the stored flag."""
+        def arr(v, dt):
+            return None if v is None else np.ascontiguousarray(v, dt).ravel()
+        xv, yv, sv, gv = arr(x, np.uint32), arr(y, np.uint32), arr(score, np.uint64), arr(is_good, np.uint8)
+        vc = arr(vertex_class, np.int32)
+        lens = {len(v) for v in (xv, yv, sv, gv) if v is not None}
+        if len(lens) > 1:
+            raise ValueError("x, y, score and is_good must be of equal length")
+        if vc is not None and len(vc) != self.lookup_sizes().n_reads:
+            raise ValueError("vertex_class must hold one value per read of the lookup result")
+        ps, pg, pb = _u64p(), _u64p(), _u64p()
+        r = C.c_uint64()
+        # (an empty list is still a given list: NULL would mean the ctx's result)
+        ptr = lambda v, ct: None if v is None else _p(v if len(v) else np.zeros(1, v.dtype), ct)
+        _ck(lib().hga_connections_quality(self._h, ptr(xv, C.c_uint32), ptr(yv, C.c_uint32), ptr(sv, C.c_uint64),
+                                          ptr(gv, C.c_uint8), lens.pop() if lens else 0, 1 if per_candidate else 0,
+                                          ptr(vc, C.c_int32), C.byref(ps), C.byref(pg), C.byref(pb), C.byref(r)))
+        free = lib().hga_free
+        return (_take(ps, r.value, np.uint64, free), _take(pg, r.value, np.uint64, free),
+                _take(pb, r.value, np.uint64, free))
+
     # ---- read overlaps (approximate_read_overlap on the lookup's first-occurrence lists)
     def read_overlaps(self, x, y):
         """(overlap int32[n], shared uint32[n]) of the ReadID pairs (x[i], y[i])."""
@@ -792,6 +826,14 @@ CLUSTER_SYMBOLS = {
     "hgc_cluster_batched": (C.c_int, [C.c_char_p, _u64p, _i32p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p,
                                       _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32, C.POINTER(ClusterConfig), C.c_int,
                                       C.POINTER(_u32p), _u64p, C.POINTER(_u32p), C.POINTER(_vp), C.c_int, _u64p]),
+    "hgc_cluster_plots": (C.c_int, [C.c_char_p, _u64p, _i32p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p,
+                                    _u64p, _u32p, _u32p, _u64p, _u32p, C.c_uint32, C.POINTER(ClusterConfig), C.c_int,
+                                    C.POINTER(_u32p), _u64p, C.POINTER(_u32p), C.POINTER(_vp), C.c_int, _u64p, C.c_int,
+                                    C.POINTER(_vp), _u64p, _u64p, _u64p]),
+    "hgc_plot_connection_histogram": (C.c_int, [_u64p, _u64p, _u64p, C.c_uint64, C.POINTER(_vp)]),
+    "hgc_plot_component_coverage": (C.c_int, [_u64p, _u32p, _u32p, C.c_uint64, C.POINTER(_vp)]),
+    "hgc_plot_spectral_graph": (C.c_int, [_u32p, _u32p, _u64p, _i32p, _i32p, C.c_uint64, _u64p, _u32p, C.c_uint64,
+                                          C.POINTER(_vp)]),
     "hgc_forest_calls": (C.c_uint64, []),
     "hgc_enrich_forest_calls": (C.c_uint64, []),
     "hgc_union_find": (C.c_int, [_u32p, _u32p, _u64p, C.c_uint64, _u32p, C.c_uint64, C.c_int, C.c_int,
@@ -865,9 +907,52 @@ def sym_eigen(a):
     return val, vec
 
 
+def _taken_string(p):
+    s = C.string_at(p.value).decode()
+    cluster_lib().hgc_free(p.value)
+    return s
+
+
+def plot_connection_histogram(score, good, bad) -> str:
+    """plot_connection_quality's wire string (ReadClusteringEngine.cpp:32, :122) of histogram rows."""
+    sv, gv, bv = (np.ascontiguousarray(v, np.uint64) for v in (score, good, bad))
+    out = C.c_void_p()
+    _cck(cluster_lib().hgc_plot_connection_histogram(_p(sv, C.c_uint64), _p(gv, C.c_uint64), _p(bv, C.c_uint64), len(sv),
+                                                     C.byref(out)))
+    return _taken_string(out)
+
+
+def plot_component_coverage(components) -> str:
+    """plot_read_coverage's wire string (:37-73); components: per component a list of (start, end) per read."""
+    cp = np.zeros(len(components) + 1, np.uint64)
+    cp[1:] = np.cumsum([len(c) for c in components], dtype=np.uint64)
+    st = np.ascontiguousarray([r[0] for c in components for r in c], np.uint32)
+    en = np.ascontiguousarray([r[1] for c in components for r in c], np.uint32)
+    out = C.c_void_p()
+    _cck(cluster_lib().hgc_plot_component_coverage(_p(cp, C.c_uint64), _p(st, C.c_uint32), _p(en, C.c_uint32),
+                                                   len(components), C.byref(out)))
+    return _taken_string(out)
+
+
+def plot_spectral_graph(conns, first_category, partition) -> str:
+    """plot_spectral's wire string (:77-98); conns: (x, y, score, ...), first_category: id -> the first
+    category of its component, partition: a list of id lists."""
+    x, y, s = _conn_arrays(conns)
+    cx = np.ascontiguousarray([first_category[int(v)] for v in x], np.int32)
+    cy = np.ascontiguousarray([first_category[int(v)] for v in y], np.int32)
+    pp = np.zeros(len(partition) + 1, np.uint64)
+    pp[1:] = np.cumsum([len(c) for c in partition], dtype=np.uint64)
+    ids = np.ascontiguousarray([i for c in partition for i in c], np.uint32)
+    out = C.c_void_p()
+    _cck(cluster_lib().hgc_plot_spectral_graph(_p(x, C.c_uint32), _p(y, C.c_uint32), _p(s, C.c_uint64), _p(cx, C.c_int32),
+                                               _p(cy, C.c_int32), len(x), _p(pp, C.c_uint64), _p(ids, C.c_uint32),
+                                               len(partition), C.byref(out)))
+    return _taken_string(out)
+
+
 def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None, debug=False, first_read_id=1,
                  start=None, end=None, batched_overlaps=False, stats=None, device_sets=False, device_tails=False,
-                 device_forest=False, device_enrich=False):
+                 device_forest=False, device_enrich=False, plots=None, plot_sink=True, device_quality=False):
     """run_clustering after construct_indices on the host (no device state): (component ids,
     per-read component id (0 = none), log text).  start / end: the reads' simulator coordinates
     (print_components' intervals under debug), None = 0.
@@ -884,7 +969,12 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
     stats then also receives "forest_calls".
     device_enrich: the enrichment union_find replays only the connections it would accept, taken from the
     enrichment-forest hook (the path of HGA_DEVICE_ENRICH=1), bound to the engine's host implementation;
-    stats then also receives "enrich_forest_calls"."""
+    stats then also receives "enrich_forest_calls".
+    plots: a list that receives the debug plots as (kind, wire) pairs in emission order (the engine runs with a
+    plot sink; plot_sink=False runs the same entry point without one); stats then also receives
+    "quality_calls_device" and "quality_calls_host".  device_quality: the two connection histograms come
+    through the quality hook (the path taken where the list stays on the device), bound to the engine's
+    host implementation."""
     L = cluster_lib()
     cfg = cfg or cluster_config()
     off = np.ascontiguousarray(offsets, np.uint64)
@@ -898,7 +988,12 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
     st = None if start is None else np.ascontiguousarray(start, np.uint32)
     en = None if end is None else np.ascontiguousarray(end, np.uint32)
     ove = np.zeros(2, np.uint64)
-    _cck(L.hgc_cluster_batched(bases, _p(off, C.c_uint64), _p(cat, C.c_int32),
+    entry, extra = L.hgc_cluster_batched, ()
+    if plots is not None:
+        pp, pbytes, pn, qc = C.c_void_p(), C.c_uint64(), C.c_uint64(), np.zeros(2, np.uint64)
+        entry = L.hgc_cluster_plots
+        extra = (1 if plot_sink else 0, C.byref(pp), C.byref(pbytes), C.byref(pn), _p(qc, C.c_uint64))
+    _cck(entry(bases, _p(off, C.c_uint64), _p(cat, C.c_int32),
                                None if st is None else _p(st, C.c_uint32), None if en is None else _p(en, C.c_uint32),
                                n, avg_read_length, first_read_id,
                                _p(a["hit_ptr"], C.c_uint64), _p(a["sorted_kid"], C.c_uint32), _p(a["first_ptr"], C.c_uint64),
@@ -906,8 +1001,16 @@ def cluster_host(bases: bytes, offsets, category, idx, avg_read_length, cfg=None
                                _p(a["kci_read"], C.c_uint32), len(a["kci_ptr"]) - 1, C.byref(cfg), 1 if debug else 0,
                                C.byref(ip), C.byref(ni), C.byref(op), C.byref(lp),
                                (1 if batched_overlaps else 0) | (2 if device_sets else 0) | (4 if device_tails else 0) |
-                               (8 if device_forest else 0) | (16 if device_enrich else 0),
-                               _p(ove, C.c_uint64)))
+                               (8 if device_forest else 0) | (16 if device_enrich else 0) | (32 if device_quality else 0),
+                               _p(ove, C.c_uint64), *extra))
+    if plots is not None:
+        blob = C.string_at(pp.value, pbytes.value)
+        L.hgc_free(pp.value)
+        parts = blob.split(b"\0")[:-1] if blob else []
+        assert len(parts) == 2 * pn.value
+        plots.extend((parts[2 * i].decode(), parts[2 * i + 1].decode()) for i in range(pn.value))
+        if stats is not None:
+            stats["quality_calls_device"], stats["quality_calls_host"] = int(qc[0]), int(qc[1])
     if stats is not None:
         stats["overlap_edges_batched"], stats["overlap_edges_host"] = int(ove[0]), int(ove[1])
         if device_forest:

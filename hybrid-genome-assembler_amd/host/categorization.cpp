@@ -38,6 +38,7 @@
 #include "clustering.h"
 #include "hga.h"
 #include "phase_timer.h"
+#include "plots.h"
 #include "ranks.h"
 #include "seqio.h"
 
@@ -289,6 +290,20 @@ int main(int argc, char* argv[]) {
                 for (uint64_t i = 0; i < e; ++i) out.edges[i] = {x[i], y[i]};
                 return out;
             });
+    }
+    // The debug plots (ReadClusteringEngine.cpp:759, :773, :782, :787, :798).  The reference pipes each wire
+    // string to "python scripts/plotting.py --plot <kind>", a script this build does not ship, so a plot is
+    // emitted only when HGA_PLOT_CMD names a command (a deliberate difference): the wire goes to
+    // it through run_command_with_input, its output ignored as there, with HGA_PLOT_KIND (the kind) and
+    // HGA_PLOT_SEQ (1, 2, ...) in its environment.
+    if (const char* plot_cmd = std::getenv("HGA_PLOT_CMD"); plot_cmd && *plot_cmd) {
+        const std::string cmd = plot_cmd;
+        engine.set_plot_sink([cmd, seq = 0](const char* kind, const std::string& wire) mutable {
+            setenv("HGA_PLOT_KIND", kind, 1);
+            setenv("HGA_PLOT_SEQ", std::to_string(++seq).c_str(), 1);
+            std::cout.flush();
+            hgah::run_command_with_input(cmd, wire);
+        });
     }
     tm.mark("engine_setup");
     const std::vector<hgah::ComponentID> cluster_ids = engine.run(std::cout);   // run_clustering (:699-802)

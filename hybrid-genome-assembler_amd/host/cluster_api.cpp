@@ -3,6 +3,7 @@
 // clustering and the eigensolver.  Status 0 = ok, -1 = error (hgc_last_error()).
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -87,12 +88,19 @@ void hgc_free(void* p) { std::free(p); }
 // 16 sets the enrichment-forest hook (set_device_enrich_forest) to host_enrich_forest, so that the
 // enrichment union_find replays only the connections it would accept, as under HGA_DEVICE_ENRICH=1;
 // hgc_enrich_forest_calls() then tells how many times this thread's last hgc_cluster* call took that path.
-int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
+// 32 sets the quality hook (set_device_quality) to host_quality, so that the two connection histograms of
+// the debug plots come through the hook, as where the list stays on the device; it is only ever called by
+// an engine with a plot sink (hgc_cluster_plots).
+// hgc_cluster_plots: the same run with a plot sink when with_sink != 0.  plots_out receives the plots in
+// emission order as one buffer of plots_bytes bytes, "kind\0wire\0" per plot, n_plots their number;
+// quality_calls[2] (may be null) the engine's {quality_calls_device, quality_calls_host}.
+static int cluster_run(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
                 const uint32_t* end, uint64_t n_reads,
                 uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
                 const uint64_t* first_ptr, const uint32_t* first_kid, const uint32_t* first_pos, const uint64_t* kci_ptr,
                 const uint32_t* kci_read, uint32_t n_sdk, const hgc_config* cfg, int debug, uint32_t** ids_out,
-                uint64_t* n_ids, uint32_t** comp_of_read, char** log_out, int batched, uint64_t* ov_edges) {
+                uint64_t* n_ids, uint32_t** comp_of_read, char** log_out, int batched, uint64_t* ov_edges,
+                std::string* plots, uint64_t* n_plots, uint64_t* quality_calls) {
     return guard([&] {
         hgah::RecordSet rs;
         rs.bases.append(bases, n_reads ? offsets[n_reads] : 0);
@@ -143,9 +151,25 @@ int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_
             e.set_device_enrich_forest([&e](const std::vector<hgah::ComponentID>& pivots, hgah::Score min_score) {
                 return e.host_enrich_forest(pivots, min_score);
             });
+        if (batched & 32)
+            e.set_device_quality([&e](const std::vector<hgah::ComponentID>& pivots, hgah::Score min_score, bool per_candidate) {
+                return e.host_quality(pivots, min_score, per_candidate);
+            });
+        if (plots)
+            e.set_plot_sink([&](const char* kind, const std::string& wire) {
+                plots->append(kind);
+                plots->push_back('\0');
+                plots->append(wire);
+                plots->push_back('\0');
+                ++*n_plots;
+            });
         std::ostringstream log;
         g_forest_calls = g_enrich_calls = 0;
         const auto ids = e.run(log);
+        if (quality_calls) {
+            quality_calls[0] = e.quality_calls_device();
+            quality_calls[1] = e.quality_calls_host();
+        }
         g_forest_calls = e.forest_calls();
         g_enrich_calls = e.enrich_forest_calls();
         if (ov_edges) {
@@ -160,6 +184,81 @@ int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_
         *comp_of_read = dup(owner.data(), owner.size());
         const std::string s = log.str();
         *log_out = dup(s.c_str(), s.size() + 1);
+    });
+}
+
+int hgc_cluster_batched(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
+                const uint32_t* end, uint64_t n_reads,
+                uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
+                const uint64_t* first_ptr, const uint32_t* first_kid, const uint32_t* first_pos, const uint64_t* kci_ptr,
+                const uint32_t* kci_read, uint32_t n_sdk, const hgc_config* cfg, int debug, uint32_t** ids_out,
+                uint64_t* n_ids, uint32_t** comp_of_read, char** log_out, int batched, uint64_t* ov_edges) {
+    return cluster_run(bases, offsets, category, start, end, n_reads, avg_read_length, first_read_id, hit_ptr, sorted_kid,
+                       first_ptr, first_kid, first_pos, kci_ptr, kci_read, n_sdk, cfg, debug, ids_out, n_ids, comp_of_read,
+                       log_out, batched, ov_edges, nullptr, nullptr, nullptr);
+}
+
+int hgc_cluster_plots(const char* bases, const uint64_t* offsets, const int32_t* category, const uint32_t* start,
+                const uint32_t* end, uint64_t n_reads,
+                uint64_t avg_read_length, uint32_t first_read_id, const uint64_t* hit_ptr, const uint32_t* sorted_kid,
+                const uint64_t* first_ptr, const uint32_t* first_kid, const uint32_t* first_pos, const uint64_t* kci_ptr,
+                const uint32_t* kci_read, uint32_t n_sdk, const hgc_config* cfg, int debug, uint32_t** ids_out,
+                uint64_t* n_ids, uint32_t** comp_of_read, char** log_out, int batched, uint64_t* ov_edges, int with_sink,
+                char** plots_out, uint64_t* plots_bytes, uint64_t* n_plots, uint64_t* quality_calls) {
+    std::string plots;
+    uint64_t n = 0;
+    const int st = cluster_run(bases, offsets, category, start, end, n_reads, avg_read_length, first_read_id, hit_ptr,
+                               sorted_kid, first_ptr, first_kid, first_pos, kci_ptr, kci_read, n_sdk, cfg, debug, ids_out, n_ids,
+                               comp_of_read, log_out, batched, ov_edges, with_sink ? &plots : nullptr, &n, quality_calls);
+    if (st != 0) return st;
+    return guard([&] {
+        *plots_out = dup(plots.data(), plots.size());
+        *plots_bytes = plots.size();
+        *n_plots = n;
+    });
+}
+
+// The wire-string formatters of the debug plots (host/plots.h), for the tests.  Each returns a malloc'ed
+// NUL-terminated string in *out (hgc_free).
+int hgc_plot_connection_histogram(const uint64_t* score, const uint64_t* good, const uint64_t* bad, uint64_t n, char** out) {
+    return guard([&] {
+        hgah::QualityHist h;
+        h.score.assign(score, score + n);
+        h.good.assign(good, good + n);
+        h.bad.assign(bad, bad + n);
+        const std::string s = hgah::connection_histogram(h);
+        *out = dup(s.c_str(), s.size() + 1);
+    });
+}
+
+// components: CSR over reads (comp_ptr[n_comp + 1]), start / end per listed read
+int hgc_plot_component_coverage(const uint64_t* comp_ptr, const uint32_t* start, const uint32_t* end, uint64_t n_comp,
+                                char** out) {
+    return guard([&] {
+        std::vector<hgah::ReadSpans> comps(n_comp);
+        for (uint64_t c = 0; c < n_comp; ++c)
+            for (uint64_t i = comp_ptr[c]; i < comp_ptr[c + 1]; ++i) comps[c].emplace_back(start[i], end[i]);
+        const std::string s = hgah::component_coverage(comps);
+        *out = dup(s.c_str(), s.size() + 1);
+    });
+}
+
+// cat_x / cat_y: *categories.begin() of each connection's two components; part_ptr / part_ids: the partition (CSR)
+int hgc_plot_spectral_graph(const uint32_t* x, const uint32_t* y, const uint64_t* s, const int32_t* cat_x,
+                            const int32_t* cat_y, uint64_t n, const uint64_t* part_ptr, const uint32_t* part_ids,
+                            uint64_t n_parts, char** out) {
+    return guard([&] {
+        std::vector<hgah::SpectralEdge> edges(n);
+        std::map<uint32_t, int32_t> cat;
+        for (uint64_t i = 0; i < n; ++i) {
+            edges[i] = {x[i], y[i], s[i]};
+            cat[x[i]] = cat_x[i];
+            cat[y[i]] = cat_y[i];
+        }
+        std::vector<std::vector<uint32_t>> parts(n_parts);
+        for (uint64_t p = 0; p < n_parts; ++p) parts[p].assign(part_ids + part_ptr[p], part_ids + part_ptr[p + 1]);
+        const std::string w = hgah::spectral_graph(edges, [&](uint32_t id) { return cat.at(id); }, parts);
+        *out = dup(w.c_str(), w.size() + 1);
     });
 }
 

@@ -746,8 +746,10 @@ uint64_t ClusteringEngine::device_connections_run(const std::vector<ComponentID>
 }
 
 // The sorted list stays on the device; only the connections union_find would accept come back.
-ClusteringEngine::ForestEdges ClusteringEngine::device_forest(Score min_score, uint32_t min_kmers, double keep_fraction) {
+ClusteringEngine::ForestEdges ClusteringEngine::device_forest(Score min_score, uint32_t min_kmers, double keep_fraction,
+                                                              QualityHist* quality) {
     uint64_t n = device_connections_run({}, min_score, min_kmers);
+    if (quality) *quality = device_quality(false);   // :759 plots the whole list, not the prefix
     if (keep_fraction >= 0) n = std::min<uint64_t>(n, (uint64_t)(size_t)((double)n * keep_fraction));
     ++gpu_calls_;
     uint64_t e = 0;
@@ -791,7 +793,7 @@ ClusteringEngine::ForestEdges ClusteringEngine::host_forest(Score min_score, uin
 // get_connections' merged-state branch without the fetch: the list stays on the device and only the
 // connections union_find(…, restricted = pivots, 2, -1) would accept come back.
 ClusteringEngine::ForestEdges ClusteringEngine::device_enrich_forest(const std::vector<ComponentID>& pivots,
-                                                                     Score min_score) {
+                                                                     Score min_score, QualityHist* quality) {
     std::vector<ComponentID> piv;
     for (ComponentID p : pivots)
         if (index_.count(p)) piv.push_back(p);   // (host_connections skips the others)
@@ -799,6 +801,7 @@ ClusteringEngine::ForestEdges ClusteringEngine::device_enrich_forest(const std::
     if (hga_components_connections(gpu_, piv.data(), piv.size(), min_score, &n) != HGA_OK)
         throw std::runtime_error(std::string("hga_components_connections: ") + hga_last_error());
     ++conn_dev_calls_;
+    if (quality) *quality = device_quality(true);
     uint64_t e = 0;
     if (hga_spanning_forest_restricted(gpu_, nullptr, nullptr, 0, 0, n, pivots.data(), pivots.size(), &e) != HGA_OK)
         throw std::runtime_error(std::string("hga_spanning_forest_restricted: ") + hga_last_error());
@@ -840,6 +843,83 @@ ClusteringEngine::ForestEdges ClusteringEngine::host_enrich_forest(const std::ve
         out.edges.emplace_back(c.x, c.y);
     }
     return out;
+}
+
+// plot_connection_quality (:19-31 / :102-121) up to the formatting.
+QualityHist ClusteringEngine::quality_of(const std::vector<Connection>& connections, bool per_candidate) {
+    std::map<bool, std::map<Score, uint64_t>> score_to_matching = {{true, {}}, {false, {}}};
+    if (!per_candidate) {
+        for (const Connection& c : connections) ++score_to_matching[c.is_good][c.score];
+    } else {
+        std::map<ComponentID, std::pair<Score, bool>> best_per_vertex;
+        for (const Connection& c : connections) {
+            auto it = best_per_vertex.insert({c.y, {0, false}}).first;
+            if (c.score > it->second.first) it->second = {c.score, c.is_good};
+        }
+        for (const auto& kv : best_per_vertex) ++score_to_matching[kv.second.second][kv.second.first];
+    }
+    std::map<Score, std::pair<uint64_t, uint64_t>> rows;   // score -> (good, bad)
+    for (const auto& kv : score_to_matching[true]) rows[kv.first].first = kv.second;
+    for (const auto& kv : score_to_matching[false]) rows[kv.first].second = kv.second;
+    QualityHist h;
+    for (const auto& kv : rows) {
+        h.score.push_back(kv.first);
+        h.good.push_back(kv.second.first);
+        h.bad.push_back(kv.second.second);
+    }
+    return h;
+}
+
+QualityHist ClusteringEngine::host_quality(const std::vector<ComponentID>& pivots, Score min_score, bool per_candidate) {
+    // (the list is computed again only to be counted: the engine's call counters stay those of the run)
+    const uint64_t dev = conn_dev_calls_, host = conn_host_calls_;
+    const int gpu = gpu_calls_;
+    const std::vector<Connection> conns = per_candidate ? get_connections(pivots, min_score) : get_all_connections(min_score);
+    conn_dev_calls_ = dev;
+    conn_host_calls_ = host;
+    gpu_calls_ = gpu;
+    return quality_of(conns, per_candidate);
+}
+
+QualityHist ClusteringEngine::device_quality(bool per_candidate) {
+    // after a merge is_good compares the components' category sets (:319): one class per distinct set, an
+    // id outside the index (is_good false there) a class of its own
+    std::vector<int32_t> cls;
+    if (!pristine_) {
+        cls.resize(reads_.size());
+        for (size_t i = 0; i < cls.size(); ++i) cls[i] = -1 - (int32_t)i;
+        std::map<std::set<int32_t>, int32_t> number;
+        for (const auto& kv : index_) {
+            const uint64_t i = kv.first - first_id_;
+            if (i < cls.size()) cls[i] = number.emplace(kv.second.categories, (int32_t)number.size()).first->second;
+        }
+    }
+    uint64_t *sc = nullptr, *good = nullptr, *bad = nullptr, rows = 0;
+    if (hga_connections_quality(gpu_, nullptr, nullptr, nullptr, nullptr, 0, per_candidate ? 1 : 0,
+                                pristine_ ? nullptr : cls.data(), &sc, &good, &bad, &rows) != HGA_OK)
+        throw std::runtime_error(std::string("hga_connections_quality: ") + hga_last_error());
+    QualityHist h;
+    h.score.assign(sc, sc + rows);
+    h.good.assign(good, good + rows);
+    h.bad.assign(bad, bad + rows);
+    hga_free(sc);
+    hga_free(good);
+    hga_free(bad);
+    return h;
+}
+
+// plot_read_coverage's input (:63-72): the components in the order given, their reads' simulator coordinates
+std::string ClusteringEngine::coverage_wire(const std::vector<ComponentID>& ids) const {
+    std::vector<ReadSpans> comps;
+    for (ComponentID id : ids) {
+        ReadSpans spans;
+        for (uint32_t r : index_.at(id).reads) {
+            const uint64_t i = r - first_id_;
+            spans.emplace_back(reads_.start.empty() ? 0u : reads_.start[i], reads_.end.empty() ? 0u : reads_.end[i]);
+        }
+        comps.push_back(std::move(spans));
+    }
+    return component_coverage(comps);
 }
 
 std::vector<Connection> ClusteringEngine::get_all_connections(Score min_score, double keep_fraction) {   // :335-339
@@ -1562,6 +1642,8 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
         print_components(ids, out);   // :745
         return ids;
     }
+    const bool plots = plots_on();
+    QualityHist quality;
     std::vector<Connection> scaffold_forming, conns;
     if (cfg_.scaffold_forming_score > 0) {   // :749-756
         const Score s = cfg_.scaffold_forming_score;
@@ -1573,23 +1655,55 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
             return get_connections(ids, s);
         });
         scaffold_forming = filter_connections(conns, [&](const Connection& c) { return c.score > s; });
+        if (plots) {
+            quality = quality_of(conns, false);
+            ++quality_host_calls_;
+        }
     } else if (forest_applies()) {
         // the prefix stays on the device: only the connections union_find accepts come back, in position
         // order, and its replay over them repeats the full list's merges (clustering.h)
         const ForestEdges fe = timed(out, "Calculation of connections between reads", [&] {
             const double f = cfg_.scaffold_forming_fraction;
-            return dev_forest_fn_ ? dev_forest_fn_(1, 1, f) : device_forest(1, 1, f);
+            // (the ctx's list is counted before the forest call reads it)
+            const bool on_ctx = plots && !dev_quality_fn_ && !dev_forest_fn_;
+            return dev_forest_fn_ ? dev_forest_fn_(1, 1, f) : device_forest(1, 1, f, on_ctx ? &quality : nullptr);
         });
+        if (plots) {
+            if (dev_quality_fn_) {
+                quality = dev_quality_fn_({}, 1, false);
+                ++quality_dev_calls_;
+            } else if (!dev_forest_fn_) {
+                ++quality_dev_calls_;
+            } else if (gpu_) {   // a forest hook over the ctx's gathered list (categorization --gpus N)
+                quality = device_quality(false);
+                ++quality_dev_calls_;
+            } else {
+                quality = host_quality({}, 1, false);
+                ++quality_host_calls_;
+            }
+        }
         ++forest_calls_;
         forest_conns_ = fe.connections;
         forest_edges_ = fe.edges.size();
         scaffold_forming.reserve(fe.edges.size());
         for (auto& e : fe.edges) scaffold_forming.push_back({e.first, e.second, 0, false});
+    } else if (plots && !dev_quality_fn_ && !(pristine_ && gpu_ && !dev_conn_)) {
+        // :759 plots the whole list: where it comes to the host anyway it is counted here, then cut (:755)
+        scaffold_forming = timed(out, "Calculation of connections between reads", [&] { return get_all_connections(1); });
+        quality = quality_of(scaffold_forming, false);
+        ++quality_host_calls_;
+        scaffold_forming.resize(std::min(scaffold_forming.size(),
+                                         (size_t)((double)scaffold_forming.size() * cfg_.scaffold_forming_fraction)));
     } else {
         // only the first size * fraction entries are used (:754-755): fetch just that prefix
         scaffold_forming = timed(out, "Calculation of connections between reads",
                                  [&] { return get_all_connections(1, cfg_.scaffold_forming_fraction); });
+        if (plots) {   // the whole list is still the ctx's result
+            quality = dev_quality_fn_ ? dev_quality_fn_({}, 1, false) : device_quality(false);
+            ++quality_dev_calls_;
+        }
     }
+    if (plots) plot_sink_("connection_histogram", connection_histogram(quality));   // :759
     std::set<ComponentID> restricted;
     auto comps_and_trees = timed(out, "Union-find", [&] {
         return union_find(scaffold_forming, restricted, cfg_.scaffold_component_min_size,
@@ -1603,6 +1717,12 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
         auto strong = filter_connections(core, [](const Connection& c) { return c.score > 5; });
         if (!strong.empty()) {
             auto spectral = timed(out, "Spectral clustering", [&] { return spectral_clustering(strong, cfg_.spectral_dims); });
+            if (plots) {   // :773
+                std::vector<SpectralEdge> edges;
+                for (const Connection& c : strong) edges.push_back({c.x, c.y, c.score});
+                plot_sink_("spectral_graph", spectral_graph(edges, [this](uint32_t id) { return *index_.at(id).categories.begin(); },
+                                                            spectral));
+            }
             timed(out, "Merging of scaffold components", [&] { return merge_components(spectral); });
         }
         remove_merged_components();
@@ -1610,14 +1730,28 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
     const uint64_t min_size = (uint64_t)(int64_t)cfg_.scaffold_component_min_size;   // int -> u64 as there
     auto core_ids = component_ids(min_size);
     print_components(core_ids, out);   // :781 (sorts core_ids in place, as there)
+    if (plots) plot_sink_("component_coverage", coverage_wire(core_ids));   // :782
     {   // :785-794
+        const Score es = cfg_.enrichment_connections_min_score;
         if (enrich_forest_applies()) {
             // the list stays on the device: only the connections union_find accepts come back, in position
             // order, and its replay over them with the same restricted set repeats the full list's merges
             const ForestEdges fe = timed(out, "Calculation of enrichment connections", [&] {
                 const Score s = cfg_.enrichment_connections_min_score;
-                return dev_enrich_fn_ ? dev_enrich_fn_(core_ids, s) : device_enrich_forest(core_ids, s);
+                const bool on_ctx = plots && !dev_quality_fn_ && !dev_enrich_fn_;
+                return dev_enrich_fn_ ? dev_enrich_fn_(core_ids, s) : device_enrich_forest(core_ids, s, on_ctx ? &quality : nullptr);
             });
+            if (plots) {
+                if (dev_quality_fn_) {
+                    quality = dev_quality_fn_(core_ids, es, true);
+                    ++quality_dev_calls_;
+                } else if (!dev_enrich_fn_) {
+                    ++quality_dev_calls_;
+                } else {
+                    quality = host_quality(core_ids, es, true);
+                    ++quality_host_calls_;
+                }
+            }
             ++enrich_calls_;
             enrich_conns_ = fe.connections;
             enrich_edges_ = fe.edges.size();
@@ -1627,7 +1761,17 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
         } else {
             conns = timed(out, "Calculation of enrichment connections",
                           [&] { return get_connections(core_ids, cfg_.enrichment_connections_min_score); });
+            if (plots) {
+                if (dev_quality_fn_) {
+                    quality = dev_quality_fn_(core_ids, es, true);
+                    ++quality_dev_calls_;
+                } else {   // the whole list is here
+                    quality = quality_of(conns, true);
+                    ++quality_host_calls_;
+                }
+            }
         }
+        if (plots) plot_sink_("connection_histogram", connection_histogram(quality));   // :787
         restricted.insert(core_ids.begin(), core_ids.end());
         comps_and_trees = union_find(conns, restricted, 2, -1);
         timed(out, "Merging into core components", [&] { return merge_components(extract_components(comps_and_trees)); });
@@ -1635,9 +1779,13 @@ std::vector<ComponentID> ClusteringEngine::run(std::ostream& out) {
         core_ids = component_ids(min_size);
     }
     print_components(core_ids, out);   // :797
+    if (plots) plot_sink_("component_coverage", coverage_wire(core_ids));   // :798
     if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1")
         std::fprintf(stderr, "hga-timing conn.device_calls %llu\nhga-timing conn.host_calls %llu\n",
                      (unsigned long long)conn_dev_calls_, (unsigned long long)conn_host_calls_);
+    if (const char* te = std::getenv("HGA_TIMING"); te && std::string(te) == "1")
+        std::fprintf(stderr, "hga-timing quality.device_calls %llu\nhga-timing quality.host_calls %llu\n",
+                     (unsigned long long)quality_dev_calls_, (unsigned long long)quality_host_calls_);
     if (const char* te = std::getenv("HGA_TIMING"); forest_calls_ && te && std::string(te) == "1")
         std::fprintf(stderr, "hga-timing forest.device_calls %llu\nhga-timing forest.connections %llu\nhga-timing forest.edges %llu\n",
                      (unsigned long long)forest_calls_, (unsigned long long)forest_conns_,

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "hga.h"
+#include "plots.h"
 #include "seqio.h"
 
 namespace hgah {
@@ -232,12 +233,44 @@ class ClusteringEngine {
     // HGA_DEVICE_ENRICH=1 without HGA_HOST_CONNECTIONS=1: what an engine with a ctx runs.
     static bool device_enrich_requested();
     uint64_t enrich_forest_calls() const { return enrich_calls_; }
+    // The debug plots (:759, :773, :782, :787, :798).  With a sink set, run() under debug hands it the wire
+    // string of each plot the reference pipes to scripts/plotting.py, at the reference's sites and in its
+    // order, with the kinds "connection_histogram" (:759), "spectral_graph" (:773, only when the spectral
+    // stage runs), "component_coverage" (:782), "connection_histogram" (:787), "component_coverage" (:798);
+    // force_spectral emits nothing (:739-746).  Without a sink nothing is computed and run() makes the calls
+    // it made before, one for one.
+    // The two connection histograms are statistics over a whole connection list.  Where the engine holds
+    // that list (the host path, before it is cut to the scaffold-forming fraction; a connection hook's
+    // fetch; get_connections' fetch for the enrichment) it counts on the host; where the list stays on the
+    // device (the first pass's prefix fetch, HGA_DEVICE_FOREST=1, HGA_DEVICE_ENRICH=1) it calls
+    // hga_connections_quality on the ctx's result, for the enrichment with one class per id numbering the
+    // components' distinct category sets (is_good compares those sets, :319, and only the host holds them).
+    using PlotSink = std::function<void(const char* kind, const std::string& wire)>;
+    void set_plot_sink(PlotSink fn) { plot_sink_ = std::move(fn); }
+    // fn(pivots, min_score, per_candidate) -> the histogram of the list the site plots in the current state:
+    // per_candidate false (:759): get_all_connections(min_score), every row, pivots not read;
+    // per_candidate true (:787): get_connections(pivots, min_score), the best row per candidate.
+    // Replaces both the device call and the host count at :787, and at :759 on the fraction path (with
+    // scaffold_forming_score > 0 the whole list is on the host and is counted there).
+    using DeviceQuality = std::function<QualityHist(const std::vector<ComponentID>& pivots, Score min_score, bool per_candidate)>;
+    void set_device_quality(DeviceQuality fn) { dev_quality_fn_ = std::move(fn); }
+    // The hook's semantics on the host (the hook of the device-less tests): the list, then quality_of.
+    QualityHist host_quality(const std::vector<ComponentID>& pivots, Score min_score, bool per_candidate);
+    // plot_connection_quality's two loops (:19-31, :102-121) over an ordered list.
+    static QualityHist quality_of(const std::vector<Connection>& connections, bool per_candidate);
+    uint64_t quality_calls_device() const { return quality_dev_calls_; }
+    uint64_t quality_calls_host() const { return quality_host_calls_; }
 
    private:
+    bool plots_on() const { return debug_ && (bool)plot_sink_; }
+    // hga_connections_quality on the ctx's current connection result
+    QualityHist device_quality(bool per_candidate);
+    std::string coverage_wire(const std::vector<ComponentID>& ids) const;
     bool forest_applies() const;
     bool enrich_forest_applies() const;
-    ForestEdges device_enrich_forest(const std::vector<ComponentID>& pivots, Score min_score);
-    ForestEdges device_forest(Score min_score, uint32_t min_kmers, double keep_fraction);
+    // quality (may be null): filled from the list on the device, before the forest call reads it
+    ForestEdges device_enrich_forest(const std::vector<ComponentID>& pivots, Score min_score, QualityHist* quality = nullptr);
+    ForestEdges device_forest(Score min_score, uint32_t min_kmers, double keep_fraction, QualityHist* quality = nullptr);
     // hga_connections_run of the pristine state as get_connections calls it; returns the list's length
     uint64_t device_connections_run(const std::vector<ComponentID>& pivots, Score min_score, uint32_t min_kmers);
     bool sets_mode() const;
@@ -284,6 +317,9 @@ class ClusteringEngine {
     DeviceEnrichForest dev_enrich_fn_;
     bool dev_enrich_ = false;   // HGA_DEVICE_ENRICH=1 with the component state on the device
     uint64_t enrich_calls_ = 0, enrich_conns_ = 0, enrich_edges_ = 0;
+    PlotSink plot_sink_;
+    DeviceQuality dev_quality_fn_;
+    uint64_t quality_dev_calls_ = 0, quality_host_calls_ = 0;
     uint64_t ov_edges_dev_ = 0, ov_edges_host_ = 0;
     bool pristine_ = true;   // no merge yet: the device indices still describe the state
     int gpu_calls_ = 0;

@@ -49,6 +49,7 @@
 #include "hga.h"
 #include "kmer_analysis.h"
 #include "phase_timer.h"
+#include "plots.h"
 #include "ranks.h"
 #include "seqio.h"
 
@@ -58,21 +59,7 @@ void check(hga_status s, const char* what) {
     if (s != HGA_OK) throw std::runtime_error(std::string(what) + ": " + hga_last_error());
 }
 
-// run_command_with_input (src/common/Utils.cpp:24-45): popen(cmd, "w"), write, pclose.
-int run_command_with_input(const std::string& cmd, const std::string& in) {
-    std::FILE* p = popen(cmd.c_str(), "w");
-    if (!p) {
-        std::fprintf(stderr, "incorrect parameters or too many files.\n");
-        return EXIT_FAILURE;
-    }
-    std::fprintf(p, "%s", in.c_str());
-    if (std::ferror(p)) {
-        std::fprintf(stderr, "Output to stream failed.\n");
-        std::exit(EXIT_FAILURE);
-    }
-    if (pclose(p) != 0) std::fprintf(stderr, "Could not run more or other error.\n");
-    return EXIT_SUCCESS;
-}
+using hgah::run_command_with_input;   // (host/plots.cpp, shared with categorization)
 
 using hgah::PhaseTimer;
 

@@ -323,6 +323,35 @@ hga_status hga_connections_fetch(hga_ctx* ctx, uint32_t* x, uint32_t* y, uint64_
 hga_status hga_connections_fetch_range(hga_ctx* ctx, uint64_t first, uint64_t count, uint32_t* x, uint32_t* y,
                                        uint64_t* score, uint8_t* is_good);
 
+/* Connection quality — the two histograms plot_connection_quality pipes to the plotting script under -d
+ * (src/clustering/ReadClusteringEngine.cpp:19-34 and :102-124), over a whole ordered connection list
+ * where it lies: per distinct score, how many counted connections are good and how many bad.
+ * List: x == y == score == NULL: the ctx's current ordered connection result, as hga_spanning_forest
+ *   reads it (after hga_connections_run, hga_components_connections or hga_connections_gather; n and
+ *   is_good are ignored; HGA_ERR_STATE without one).  x, y and score all given: n host rows, copied;
+ *   is_good may be NULL (all 0).  The rows must be in result order, score non-increasing (checked on the
+ *   host), and every id one of the current lookup's ReadIDs; x[i] == y[i] is legal and counts like any
+ *   row.  Otherwise, and for any other NULL mix: HGA_ERR_INVALID with nothing launched.  More than
+ *   2^32 - 2 rows: HGA_ERR_INVALID (positions are 32-bit on the device).
+ * vertex_class: NULL, or n_reads entries in read order; when given, good = vertex_class[x] ==
+ *   vertex_class[y] replaces the stored flag.  (After a merge is_good compares the components' category
+ *   sets, which only the host holds: the caller numbers the distinct sets.)
+ * per_candidate == 0 (:19-34): every row counts once, under its score and its flag.
+ * per_candidate != 0 (:102-124): one count per distinct y, from the row the reference loop keeps.  The
+ *   loop replaces its entry only on a strictly larger score and the list is score-descending, so that
+ *   is the row at the smallest position among the rows with that y; where scores tie this follows the
+ *   result order's (pivot, candidate), the reference's order is unspecified there.  A kept row of score
+ *   0 counts as bad whatever its flag: the loop starts from {0, false} and never replaces it (:105-108).
+ * Result: three hga_free-able arrays of *n_rows entries: the scores strictly ascending (full 64 bits),
+ *   good and bad counts.  A score is listed only if good + bad > 0; *n_rows = 0 for an empty list.
+ * Synchronous; HGA_ERR_STATE before hga_lookup_run.  The connection result is only read. */
+hga_status hga_connections_quality(hga_ctx* ctx, const uint32_t* x, const uint32_t* y, const uint64_t* score,
+                                   const uint8_t* is_good, uint64_t n, int per_candidate,
+                                   const int32_t* vertex_class /* n_reads, or NULL */, uint64_t** out_score,
+                                   uint64_t** out_good, uint64_t** out_bad, uint64_t* n_rows);
+/* Rows per workgroup of its kernels (the sizes at which the tests change paths). */
+uint32_t hga_connections_quality_tile(void);
+
 /* ------------------------------------------------------------------------------
  * Read overlaps — ReadClusteringEngine::approximate_read_overlap as get_spanning_tree_tails
  * calls it per spanning-tree edge (src/clustering/ReadClusteringEngine.cpp:491-513), for n
