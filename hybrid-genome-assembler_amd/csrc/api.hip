@@ -84,6 +84,8 @@ hga_status hga_ctx_create(hga_ctx** out, int device) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             c->num_cu = prop.multiProcessorCount;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.totalGlobalMem > 0)
+            c->total_mem = prop.totalGlobalMem;
         hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
             delete c;
@@ -233,6 +235,31 @@ hga_status hga_count_add_rows(hga_ctx* c, uint32_t file, const uint64_t* keys, c
 
 hga_status hga_count_run(hga_ctx* c, uint32_t min_per_file) {
     HGA_CTX_GUARD(c, hga::count_run(c, min_per_file));
+}
+
+hga_status hga_count_set_passes(hga_ctx* c, uint32_t passes, uint64_t budget_bytes) {
+    HGA_CTX_GUARD(c, hga::count_set_passes(c, passes, budget_bytes));
+}
+
+hga_status hga_count_estimate(hga_ctx* c, uint32_t min_per_file, uint32_t passes, uint64_t* bytes) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(bytes, HGA_ERR_INVALID, "null out pointer");
+        *bytes = hga::count_estimate(c, min_per_file, passes);
+    });
+}
+
+hga_status hga_count_get_pass_stats(hga_ctx* c, hga_count_pass_stats* out) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(out, HGA_ERR_INVALID, "null out pointer");
+        auto& s = c->count;
+        hga::count_settle(c);
+        HGA_REQUIRE(s.ran, HGA_ERR_STATE, "hga_count_run not called");
+        out->passes = s.run_passes;
+        out->pad = 0;
+        out->work_bytes = s.work_bytes;
+        out->max_pass_instances = s.pass_max;
+        out->min_pass_instances = s.pass_min;
+    });
 }
 
 hga_status hga_count_get_stats(hga_ctx* c, hga_count_stats* out) {

@@ -30,6 +30,7 @@
 #include <map>
 #include <type_traits>
 
+#include "count_sizing.hpp"
 #include "hga_internal.hpp"
 #include "kmer_dev.hpp"
 
@@ -94,11 +95,18 @@ struct KP {
     uint64_t mask;
     Mix mix;
     uint32_t fb, rbits, nb;      // fine buckets: top fb bits; remainder = low rbits bits
+    uint32_t pp;                 // key-range passes: this pass (the key's bits from psh up); 0 with one pass
     uint64_t rmask;
     uint32_t fb1, r1bits, nb1;   // level-1 regions: top fb1 bits; element = low r1bits bits
+    uint32_t psh;                // key bits below the pass bits (fb + rbits); 0 with one pass
     uint64_t r1mask;
     uint32_t fb2, nb2;           // level-2 digit: the next fb2 bits
 };
+// (pp and psh sit where the struct had padding: the single-pass kernels' arguments keep their offsets)
+static_assert(sizeof(KP) == 120 && offsetof(KP, rmask) == 80 && offsetof(KP, r1mask) == 104, "KP layout");
+// The pass's key prefix in place: with more than one pass, fb / rbits (and region_of / bucket_of)
+// describe the psh bits below it, and the kernels that rebuild a key OR this back in.
+__host__ __device__ __forceinline__ uint64_t pass_prefix(const KP& kp) { return (uint64_t)kp.pp << kp.psh; }
 
 __device__ __forceinline__ uint32_t bucket_of(uint64_t h, const KP& kp) {
     return kp.fb ? (uint32_t)(h >> kp.rbits) : 0u;
@@ -218,7 +226,11 @@ struct BinFile {
 // spill out of the SGPR file (v_readlane per use) and runs_of is a chain of uniform selects.
 // FB > 0 (with K): the fine-bucket bits known at compile time too (C2-sized inputs: 12), so region and
 // bucket are constant shifts of the mixed key (no 64-bit shift by a uniform register per window).
-template <class E1, int K = 0, int FB = 0>
+// PASS: one of several key-range passes (count_run): a window counts only if its mixed key's bits
+// from kp.psh up equal kp.pp; region, bucket and element come from the bits below (masked: the
+// h < 4^k shortcuts do not hold under a pass prefix).  A window of another pass goes where an invalid
+// one goes and adds nothing to cnt1, fhist or inst.  The PASS = false instantiations are untouched.
+template <class E1, int K = 0, int FB = 0, bool PASS = false>
 __global__ void __launch_bounds__(NT_B, HGA_B1_WAVES) kc_bin1(const BinFile* __restrict__ files, uint32_t F,
                                                 uint64_t st_pos, KP kp,
                                                 Blk* __restrict__ table, uint64_t table_cap,
@@ -264,6 +276,7 @@ __global__ void __launch_bounds__(NT_B, HGA_B1_WAVES) kc_bin1(const BinFile* __r
     const uint64_t end = start + st_pos < n ? start + st_pos : n;
     uint32_t inst = 0;
     static_assert(P_B == 16 && Frame<P_B>::NW == 3, "one packed word per thread, frames of three");
+    static_assert(!(PASS && FB), "the pass variant takes its shifts from kp");
     const uint8_t* __restrict__ seq = files[file].seq;
     const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
     // tile t's words are packed into lpw[t & 1] while tile t-1 is binned, so the tile's own
@@ -310,6 +323,7 @@ __global__ void __launch_bounds__(NT_B, HGA_B1_WAVES) kc_bin1(const BinFile* __r
         const uint32_t wm = (uint32_t)(runs_of(v64, kk) >> 32);   // bit j: window at p0+j valid
         uint32_t dd[P_B], rk[P_B];
         E1 ee[P_B];
+        uint32_t okm = 0;   // (PASS) bit j: the window at p0+j is valid and of this pass
         const uint64_t wmask = K ? (K >= 32 ? ~0ull : ((1ull << (2 * K)) - 1)) : kp.mask;
         Mix mx = kp.mix;
         if (K) {
@@ -327,24 +341,33 @@ __global__ void __launch_bounds__(NT_B, HGA_B1_WAVES) kc_bin1(const BinFile* __r
             // byte offset in its stage run and dd the region's byte offset in the counter / run-offset
             // arrays (the stage needs no index scaling).  An invalid window is staged into this lane's
             // dummy slot TP_B + lane: "region" 0 (whose run offset is 0) with that rank.
-            const bool ok = (wm >> j) & 1u;
-            const uint32_t reg = K && K < 32 ? (uint32_t)(h >> r1s) : region_of(h, kp);
+            bool ok = (wm >> j) & 1u;
+            uint32_t reg;
+            uint64_t hl = h;   // the key below the pass bits
+            if constexpr (PASS) {
+                ok = ok && (uint32_t)(h >> kp.psh) == kp.pp;   // (1 <= psh <= 63)
+                hl = h & ((1ull << kp.psh) - 1ull);
+                reg = region_of(hl, kp);
+                okm |= (uint32_t)ok << j;
+            } else {
+                reg = K && K < 32 ? (uint32_t)(h >> r1s) : region_of(h, kp);
+            }
             dd[j] = ok ? reg * 4u : 0u;
             // (u32 elements of a k with 2k - MAX_FB1 >= 32: r1bits == 32, the truncation is the mask)
-            constexpr bool trunc = K && sizeof(E1) == 4 && 2 * K - MAX_FB1 >= 32;
+            constexpr bool trunc = !PASS && K && sizeof(E1) == 4 && 2 * K - MAX_FB1 >= 32;
             ee[j] = trunc ? (E1)h : (E1)(h & kp.r1mask);
             rk[j] = ((uint32_t)TP_B + (uint32_t)(tid & 63)) * (uint32_t)sizeof(E1);
             if (HGA_B1_BRANCHFREE) {   // invalid windows count into this lane's dummy counters
                 const uint32_t r = atomicAdd(&cnt1[ok ? reg : NB1_MAX + (uint32_t)(tid & 63)], (uint32_t)sizeof(E1));
-                atomicAdd(&fhist[ok ? (K && K < 32 ? (uint32_t)(h >> kp.rbits) : bucket_of(h, kp))
+                atomicAdd(&fhist[ok ? (!PASS && K && K < 32 ? (uint32_t)(h >> kp.rbits) : bucket_of(hl, kp))
                                     : MAX_NB + (uint32_t)(tid & 63)], 1u);
                 if (ok) rk[j] = r;
             } else if (ok) {
                 rk[j] = atomicAdd(&cnt1[reg], (uint32_t)sizeof(E1));
-                atomicAdd(&fhist[K && K < 32 ? (uint32_t)(h >> rbs) : bucket_of(h, kp)], 1u);
+                atomicAdd(&fhist[!PASS && K && K < 32 ? (uint32_t)(h >> rbs) : bucket_of(hl, kp)], 1u);
             }
         }
-        inst += __popc(wm);
+        inst += __popc(PASS ? okm : wm);
         lds_barrier();
         if (tid < 64) {   // one wave: scan the <= 64 region counts, place them in the blocks
             const uint32_t c = tid < (int)nb1 ? cnt1[tid] / (uint32_t)sizeof(E1) : 0u;   // (byte units)
@@ -425,6 +448,31 @@ __global__ void __launch_bounds__(NT_B, HGA_B1_WAVES) kc_bin1(const BinFile* __r
 // Pipeline counters: gstat[3] = the first spill block, the rest 0.
 __global__ void kc_init_stat(unsigned long long* __restrict__ gstat, uint64_t n_first) {
     if (threadIdx.x < 8) gstat[threadIdx.x] = threadIdx.x == 3 ? (unsigned long long)n_first : 0ull;
+}
+// Between two key-range passes (count_run): cum[p] = the instances of passes 0..p; the block cursor
+// and the listed-bucket count start over, the row cursor [0], the largest split [1], the error bits
+// [2] and the instances [4] carry on.
+__global__ void kc_pass_next(unsigned long long* __restrict__ gstat, uint64_t n_first,
+                             unsigned long long* __restrict__ cum, uint32_t p) {
+    if (threadIdx.x == 0) {
+        cum[p] = gstat[4];
+        gstat[3] = (unsigned long long)n_first;
+        gstat[5] = 0ull;
+    }
+}
+// A pass whose key range holds more instances (the end of the last bucket's run) than `binned` has
+// room for: error bit 8, and every bucket run made empty so that nothing downstream reads or writes
+// past a buffer (kc_rebin<.., true> leaves at once on the bit; the split and count kernels see empty
+// buckets).  Two launches: the bit, then the runs.
+__global__ void kc_pass_guard(const uint64_t* __restrict__ fs, uint64_t n_fs, uint64_t binned_cap,
+                              unsigned long long* __restrict__ gstat) {
+    if (threadIdx.x == 0 && fs[n_fs - 1] > binned_cap) atomicOr(&gstat[2], 8ull);
+}
+__global__ void __launch_bounds__(256) kc_pass_void(uint64_t* __restrict__ fs, uint64_t n_fs,
+                                                    const unsigned long long* __restrict__ gstat) {
+    if (!(gstat[2] & 8ull)) return;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_fs) fs[i] = 0;
 }
 // ---------------------------------------------------------------- layout
 // (more than LAYOUT_W_MAX bin1 workgroups; else sort.hip's layout_scan reads wcnt transposed itself)
@@ -715,13 +763,17 @@ __device__ __forceinline__ void rebin_block(const uint64_t blk, const E1* __rest
 // grid-stride (at C2 there are none, and a grid of every possible spill block retired ~36 K empty
 // workgroups).  First and spill blocks of one chain share their slot range atomically (rebin_block),
 // so their order does not matter.
-template <class E1, class E>
+// CLIP (key-range passes): nothing is written once kc_pass_guard has found the pass too heavy for `out`.
+template <class E1, class E, bool CLIP = false>
 __global__ void __launch_bounds__(NT_R_MAX) kc_rebin(const E1* __restrict__ in1, const Blk* __restrict__ table,
                                                  const unsigned long long* __restrict__ gstat, uint32_t W,
                                                  KP kp, const uint32_t* __restrict__ nblk,
                                                  unsigned long long* __restrict__ off,
                                                  E* __restrict__ out) {
     const uint64_t n_first = (uint64_t)W * kp.nb1;
+    if constexpr (CLIP) {
+        if (gstat[2] & 8ull) return;
+    }
     if (blockIdx.x < n_first) {
         rebin_block<E1, E>(blockIdx.x, in1, table, W, kp, nblk, off, out);
         return;
@@ -1049,7 +1101,7 @@ __global__ void __launch_bounds__(NT_C) kc_count(const E* __restrict__ binned,
             if (base + tot > cap) {
                 if (tid == 0 && tot) atomicOr(&gstat[2], 2ull);
             } else {
-                const uint64_t hb = kp.fb ? ((uint64_t)b << rbits) : 0ull;
+                const uint64_t hb = (kp.fb ? ((uint64_t)b << rbits) : 0ull) | pass_prefix(kp);
                 for (uint32_t j = tid; j < tot; j += NT_C) {
                     out_key[base + j] = mix_inv(hb | (uint64_t)sk[j], kp.mix);
                     for (uint32_t ff = 0; ff < F; ++ff) out_cnt[(size_t)ff * cap + base + j] = sc[(size_t)ff * T + j];
@@ -1079,7 +1131,7 @@ __global__ void __launch_bounds__(NT_C) kc_count(const E* __restrict__ binned,
                 base = __shfl(base, 63, 64);
                 if (!np) continue;
                 uint64_t at = (uint64_t)base + inc - np;
-                const uint64_t h = (kp.fb ? ((uint64_t)b << rbits) : 0ull) | (uint64_t)r;
+                const uint64_t h = (kp.fb ? ((uint64_t)b << rbits) : 0ull) | pass_prefix(kp) | (uint64_t)r;
                 while (c0 | c1) {   // one piece, or several adjacent ones past the piece width
                     const uint32_t q0 = min(c0, xe.cmax), q1 = min(c1, xe.cmax);
                     slab[at++] = h | ((uint64_t)q0 << xe.kb) | ((uint64_t)q1 << (xe.kb + xe.cb));
@@ -1116,7 +1168,7 @@ __global__ void __launch_bounds__(NT_C) kc_count(const E* __restrict__ binned,
                 bool any = false;
                 for (uint32_t ff = 0; ff < F; ++ff) any |= cnt[(size_t)ff * T + i] >= mc;
                 if (!any) continue;
-                const uint64_t h = (kp.fb ? ((uint64_t)b << rbits) : 0ull) | (uint64_t)r;
+                const uint64_t h = (kp.fb ? ((uint64_t)b << rbits) : 0ull) | pass_prefix(kp) | (uint64_t)r;
                 out_key[o] = mix_inv(h, kp.mix);
                 for (uint32_t ff = 0; ff < F; ++ff) {
                     const uint32_t c = cnt[(size_t)ff * T + i];
@@ -1490,7 +1542,7 @@ __global__ void __launch_bounds__(NT_P, HGA_CS_WAVES) kc_count_s(const uint32_t*
             }
         __syncthreads();
         const uint64_t base = s_base;
-        const uint64_t hb = kp.fb ? ((uint64_t)b << rbits) : 0ull;
+        const uint64_t hb = (kp.fb ? ((uint64_t)b << rbits) : 0ull) | pass_prefix(kp);
         if (xep) {   // no dense rows: kc_xb_dense writes them from the pieces if a local query needs them
         } else if (base + tot > cap) {
             if (tid == 0 && tot) atomicOr(&gstat[2], 2ull);
@@ -2418,6 +2470,78 @@ void count_add(hga_ctx* c, uint32_t file, const char* seq, uint64_t n) {
     s.dist = false;
 }
 
+// The environment's test / tuning hooks that bear on sizes.
+sizing::Hooks count_hooks() {
+    sizing::Hooks hk;
+    hk.legacy = std::getenv("HGA_COUNT_LEGACY") != nullptr;   // test hook: generic kc_count for F <= 2
+    if (const char* e = std::getenv("HGA_FB_MAX")) hk.fb_max = std::min<uint32_t>(MAX_FB, (uint32_t)std::atoi(e));
+    // HGA_FB_MIN (test hook): at least that many bucket bits, so small inputs take the paths of large
+    // ones (the exchange emission needs fb >= 10)
+    if (const char* e = std::getenv("HGA_FB_MIN")) hk.fb_min = (uint32_t)std::atoi(e);
+    if (const char* e = std::getenv("HGA_B1_SOLE")) hk.sole = std::atoi(e) != 0;
+    if (const char* e = std::getenv("HGA_ROW_CAP")) hk.row_cap = std::max<uint64_t>(4, std::strtoull(e, nullptr, 10));   // test hook
+    if (const char* e = std::getenv("HGA_SPLIT3_TARGET")) hk.split3_target = std::strtoull(e, nullptr, 10);
+    if (const char* e = std::getenv("HGA_SPLIT3_FORCE")) hk.split3_force = std::max(0, std::atoi(e));   // tests: split small inputs too
+    return hk;
+}
+
+// The device bytes of the count's work buffers as they stand (what a new run can reuse or release).
+uint64_t count_held_bytes(const CountState& s) {
+    uint64_t b = 0;
+    for (const DevBuf* d : {&s.cursor, &s.file_start, &s.fine_hist, &s.cursor2, &s.nblk, &s.bin_files, &s.binned, &s.binned1,
+                            &s.regions, &s.binned3, &s.file_start3, &s.rows_key, &s.rows_cnt, &s.blist, &s.pass_cum})
+        b += d->cap;
+    return b;
+}
+
+// The sizes of the next run (count_sizing.hpp): one function for hga_count_estimate and count_run.
+// query_free: with no budget configured, look at the device's free memory when one pass takes more
+// than a quarter of the card (smaller requests are tried as they always were).
+sizing::Plan count_plan(hga_ctx* c, uint32_t min_per_file, uint32_t passes, bool query_free) {
+    auto& s = c->count;
+    const sizing::Hooks hk = count_hooks();
+    uint64_t budget = s.cfg_budget;
+    if (!passes && !budget) {
+        if (!query_free || c->comm) passes = 1;
+        else {
+            const sizing::Plan one = sizing::plan(s.k, s.n_files, s.seq_len.data(), min_per_file, (uint32_t)c->num_cu, hk, 1);
+            if (one.work_bytes <= c->total_mem / 4) return one;
+            size_t fr = 0, tot = 0;
+            HGA_HIP(hipMemGetInfo(&fr, &tot));
+            // free now + what this run's buffers already hold, less 1/32 of the card (fragmentation, the
+            // queries' buffers that follow the count)
+            const uint64_t avail = (uint64_t)fr + count_held_bytes(s), margin = (uint64_t)tot / 32;
+            if (one.work_bytes + margin <= avail) return one;
+            // the smallest P that fits, at the base margin (a budget of the caller's also widens the margin)
+            const uint32_t pmax = 1u << sizing::clamp_pb(s.k, 31);
+            sizing::Plan pl = one;
+            for (uint32_t P = 2; P <= pmax; P <<= 1) {
+                pl = sizing::plan(s.k, s.n_files, s.seq_len.data(), min_per_file, (uint32_t)c->num_cu, hk, P);
+                if (pl.work_bytes + margin <= avail) break;
+            }
+            return pl;
+        }
+    }
+    bool fits = true;
+    const sizing::Plan pl =
+        sizing::plan_run(s.k, s.n_files, s.seq_len.data(), min_per_file, (uint32_t)c->num_cu, hk, passes, budget, &fits);
+    HGA_REQUIRE(fits, HGA_ERR_OOM,
+                "the count's work buffers (" + std::to_string(pl.work_bytes) + " bytes at " + std::to_string(pl.P) +
+                    " passes) do not fit the budget of " + std::to_string(budget) + " bytes");
+    return pl;
+}
+
+void count_set_passes(hga_ctx* c, uint32_t passes, uint64_t budget) {
+    HGA_REQUIRE(passes <= (1u << 30), HGA_ERR_INVALID, "passes out of range");
+    c->count.cfg_passes = passes;
+    c->count.cfg_budget = budget;
+}
+
+uint64_t count_estimate(hga_ctx* c, uint32_t min_per_file, uint32_t passes) {
+    HGA_REQUIRE(c->count.begun, HGA_ERR_STATE, "hga_count_begin not called");
+    return count_plan(c, min_per_file, passes, false).work_bytes;
+}
+
 void count_run(hga_ctx* c, uint32_t min_per_file) {
     auto& s = c->count;
     HGA_REQUIRE(s.begun, HGA_ERR_STATE, "hga_count_begin not called");
@@ -2426,30 +2550,29 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     s.pending = false;
     const uint32_t F = s.n_files;
     s.min_per_file = min_per_file;
-    uint64_t total_bytes = 0;
-    for (auto l : s.seq_len) total_bytes += l;
+    // every size-derived choice (count_sizing.hpp): one pass as ever, or P key-range passes
+    const sizing::Plan pl = count_plan(c, min_per_file, s.cfg_passes, true);
+    const uint32_t P = pl.P;
+    HGA_REQUIRE(P == 1 || !c->comm, HGA_ERR_STATE,
+                "key-range passes are not supported on a ctx with a communicator (hga_count_set_passes(ctx, 1, 0))");
+    const uint64_t total_bytes = pl.total_bytes;
+    const uint64_t pass_bytes = pl.pass_bytes;   // expected instances of one pass
 
     KP kp{};
     kp.k = s.k;
     kp.sh = 2 * (s.k - 1);
     kp.mask = s.k >= 32 ? ~0ull : ((1ull << (2 * s.k)) - 1);
     kp.mix = make_mix(s.k);
-    const uint32_t nbits = 2u * (uint32_t)s.k;
+    const uint32_t nbits = pl.nbits;   // 2k less the pass bits
+    kp.psh = P > 1 ? nbits : 0u;
     // fan-out: ~16K windows per fine bucket, at most 8192 buckets, never more bits than the key
     // packed-count counting (kc_count_s): F <= 2 and u32 remainders; ~64K windows per bucket
-    const bool legacy = std::getenv("HGA_COUNT_LEGACY") != nullptr;   // test hook: generic kc_count for F <= 2
-    const bool packed = F <= 2 && nbits - std::min<uint32_t>(MAX_FB, nbits) <= 31 && !legacy;
-    const uint64_t per_bucket = packed ? HGA_PB_P : 16384;
-    uint32_t fb = 0, fb_max = MAX_FB;
-    if (const char* e = std::getenv("HGA_FB_MAX")) fb_max = std::min<uint32_t>(MAX_FB, (uint32_t)std::atoi(e));
-    // HGA_FB_MIN (test hook): at least that many bucket bits, so small inputs take the paths of large
-    // ones (the exchange emission needs fb >= 10)
-    const uint32_t fb_min = std::getenv("HGA_FB_MIN") ? (uint32_t)std::atoi(std::getenv("HGA_FB_MIN")) : 0u;
-    while (fb < fb_max && fb < nbits && ((total_bytes >> fb) > per_bucket || fb < fb_min)) ++fb;
+    const bool packed = pl.packed;
+    const uint64_t per_bucket = pl.per_bucket;
     // k = 32 never runs without a bucket bit (the hooks included): with fb == 0 the remainder is the whole
     // 64-bit mixed key, and the one 32-mer that mixes to all ones would equal kc_count<uint64_t>'s EMPTY
     // (the empty-slot marker and batch padding) and be dropped; a remainder of <= 63 bits cannot
-    if (nbits == 64 && fb == 0) fb = 1;
+    const uint32_t fb = pl.fb;
     kp.fb = fb;
     kp.nb = 1u << fb;
     kp.rbits = nbits - fb;
@@ -2468,15 +2591,11 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
 
     // super-tiles: ~2 per CU over all files (one resident wave of bin1 workgroups, so each
     // (workgroup, region) fills about one level-1 block), whole tiles
-    uint64_t st_pos = total_bytes / ((uint64_t)c->num_cu * HGA_B1_PER_CU) + 1;
     // far larger inputs (a C4 rank shard: 7.4 M bases per super-tile, each region's run a chain of
     // ~12 blocks) take more, smaller super-tiles instead, sized so that each (workgroup, region) still
     // fits one block: every re-bin block then writes to precomputed offsets (a chained block reserves
     // its digit runs with a returning device atomic per digit) and bin1 spills almost never
-    const uint64_t st_cap = (uint64_t)BLK * nb1 * 15 / 16;   // bases; instances <= bases
-    const char* sole_env = std::getenv("HGA_B1_SOLE");
-    if ((!sole_env || std::atoi(sole_env) != 0) && st_pos > st_cap + st_cap / 2) st_pos = st_cap;
-    st_pos = std::max<uint64_t>(ST_ALIGN, (st_pos + ST_ALIGN - 1) / ST_ALIGN * ST_ALIGN);
+    const uint64_t st_pos = pl.st_pos;
     std::vector<uint32_t> n_st(F, 0);
     std::vector<BinFile> bf(F);
     uint32_t W = 0;
@@ -2486,12 +2605,13 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
         bf[f].w0 = W;
         W += n_st[f];
     }
+    HGA_REQUIRE(W == pl.W && pl.b_tab == (sizeof(BinFile) + 4) * F, HGA_ERR_INVALID, "count sizing out of step");
 
-    auto* gstat = static_cast<unsigned long long*>(s.cursor.ensure(8 * 8));
-    uint64_t* fs = static_cast<uint64_t*>(s.file_start.ensure((size_t)nb * (F + 1) * 8));
-    uint32_t* wcnt = static_cast<uint32_t*>(s.fine_hist.ensure((size_t)std::max<uint32_t>(W, 1) * nb * 4));
-    auto* off = static_cast<unsigned long long*>(s.cursor2.ensure(((size_t)W * nb + 1) * 8));
-    uint32_t* nblk = static_cast<uint32_t*>(s.nblk.ensure((size_t)std::max<uint32_t>(W, 1) * nb1 * 4));
+    auto* gstat = static_cast<unsigned long long*>(s.cursor.ensure(pl.b_gstat));
+    uint64_t* fs = static_cast<uint64_t*>(s.file_start.ensure(pl.b_fs));
+    uint32_t* wcnt = static_cast<uint32_t*>(s.fine_hist.ensure(pl.b_wcnt));
+    auto* off = static_cast<unsigned long long*>(s.cursor2.ensure(pl.b_off));
+    uint32_t* nblk = static_cast<uint32_t*>(s.nblk.ensure(pl.b_nblk));
     for (uint32_t f = 0; f < F; ++f) bf[f].seq = s.seq[f]->as<uint8_t>();
     // per-file tables: uploaded only when they change (they are fixed for repeated runs)
     // [BinFile x F | the files' first workgroups w0 x F (the layout scan's file starts)]
@@ -2507,9 +2627,8 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     BinFile* d_bf = reinterpret_cast<BinFile*>(d_tab);
     const uint32_t* d_w0 = reinterpret_cast<const uint32_t*>(d_tab + tb);
 
-    const size_t esz1 = e1_32 ? 4 : 8, esz = e32 ? 4 : 8;
-    uint64_t cap = (total_bytes / std::max<uint32_t>(1, min_per_file) + 4) & ~3ull;   // x4: 16-B row groups
-    if (const char* e = std::getenv("HGA_ROW_CAP")) cap = std::max<uint64_t>(4, std::strtoull(e, nullptr, 10) & ~3ull);   // test hook
+    const size_t esz = e32 ? 4 : 8;
+    const uint64_t cap = pl.rows_cap;   // x4: 16-B row groups (HGA_ROW_CAP: test hook)
     const uint32_t slot_b = (uint32_t)esz + 4u * F;
     uint32_t T = 1;
     while ((uint64_t)T * 2 * slot_b <= LDS_TAB) T *= 2;
@@ -2517,32 +2636,67 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     // files all come from dump rows counts nothing, its empty buckets never fill a slot: any T will do)
     HGA_REQUIRE(T >= 2 * NT_C || total_bytes == 0, HGA_ERR_INVALID, "too many files with reads for the LDS table");
     const uint32_t maxload = std::min<uint32_t>((uint32_t)(T * 0.85), T - NT_C - 8);
-    void* binned = s.binned.ensure(std::max<size_t>(total_bytes, 1) * esz);
+    void* binned = s.binned.ensure(pl.b_binned);
 
-    // level-1 pool: one first block per (workgroup, region) + spill blocks for the worst case
+    // level-1 pool: one first block per (workgroup, region) + spill blocks for the worst case (one
+    // pass) or for the pass's share times the margin (a heavier key range sets the pool's error bit)
     const uint64_t n_first = (uint64_t)W * nb1;
-    const uint64_t table_cap = n_first + total_bytes / BLK + 2;
+    const uint64_t table_cap = pl.table_cap;
     const uint64_t pool_cap = table_cap * BLK;
-    void* binned1 = s.binned1.ensure(pool_cap * esz1);
-    Blk* table = static_cast<Blk*>(s.regions.ensure(table_cap * sizeof(Blk)));
+    HGA_REQUIRE(n_first == pl.n_first && pool_cap == pl.pool_cap, HGA_ERR_INVALID, "count sizing out of step");
+    void* binned1 = s.binned1.ensure(pl.b_binned1);
+    Blk* table = static_cast<Blk*>(s.regions.ensure(pl.b_table));
+    static_assert(sizeof(Blk) == sizing::kBlkEntryBytes && sizeof(BinFile) == sizing::kBinFileBytes && BLK == sizing::kBlk &&
+                      MAX_FB == (int)sizing::kMaxFb && MAX_FB1 == (int)sizing::kMaxFb1 && MAX_SF3 == sizing::kMaxSf3 &&
+                      SLACK_3 == sizing::kSlack3 && ST_ALIGN == sizing::kBlk,
+                  "count_sizing.hpp repeats these");
+    // the instances of passes 0..p, for the pass statistics
+    auto* pass_cum = static_cast<unsigned long long*>(s.pass_cum.ensure(pl.b_pinst));
+    void* binned3_buf = pl.fb3 ? s.binned3.ensure(pl.b_binned3) : nullptr;
+    uint64_t* fs3_buf = pl.fb3 ? static_cast<uint64_t*>(s.file_start3.ensure(pl.b_fs3)) : nullptr;
+    s.run_passes = P;
+    s.run_budget = s.cfg_budget;
+    s.work_bytes = pl.work_bytes;
+    // The passes: each a complete count of the keys whose top bits are p, queued one behind the other
+    // on the stream (the buffers are reused in stream order, no host wait); rows accumulate behind
+    // the one row cursor.  With one pass this loop body is the pipeline as it always was.
+    const KP kp0 = kp;
+    void* const binned0 = binned;
+    uint64_t* const fs0 = fs;
+    for (uint32_t pass = 0; pass < P; ++pass) {
+    kp = kp0;
+    kp.pp = pass;
+    binned = binned0;
+    fs = fs0;
     // pipeline counters (the ASCII bases are packed inside kc_bin1)
-    c->launch("kc_init", [&] { hipLaunchKernelGGL(kc_init_stat, dim3(1), dim3(64), 0, c->stream, gstat, n_first); });
+    c->launch("kc_init", [&] {
+        if (pass == 0) hipLaunchKernelGGL(kc_init_stat, dim3(1), dim3(64), 0, c->stream, gstat, n_first);
+        else hipLaunchKernelGGL(kc_pass_next, dim3(1), dim3(64), 0, c->stream, gstat, n_first, pass_cum, pass - 1);
+    });
     c->check_launch("kc_init");
 
     // B1: level-1 binning of every file into pool blocks + per-workgroup fine histograms
     if (W) {
         c->launch("kc_bin1", [&] {
-#define HGA_BIN1(E1T, KK, FBB)                                                                              \
-    hipLaunchKernelGGL((kc_bin1<E1T, KK, FBB>), dim3(W), dim3(NT_B), 0, c->stream, d_bf, F, st_pos, kp, table, table_cap, \
+#define HGA_BIN1(E1T, KK, FBB, PS)                                                                              \
+    hipLaunchKernelGGL((kc_bin1<E1T, KK, FBB, PS>), dim3(W), dim3(NT_B), 0, c->stream, d_bf, F, st_pos, kp, table, table_cap, \
                        pool_cap, static_cast<E1T*>(binned1), wcnt, nblk, gstat)
             // compile-time k for the k of the configs (C1-C4: 19; C5: 15, 17, 19, 21)
-            if (e1_32 && kp.k == 19 && kp.fb == MAX_FB && !HGA_B1_NOFB) HGA_BIN1(uint32_t, 19, MAX_FB);
-            else if (e1_32 && kp.k == 19) HGA_BIN1(uint32_t, 19, 0);
-            else if (e1_32 && kp.k == 17) HGA_BIN1(uint32_t, 17, 0);
-            else if (e1_32 && kp.k == 15) HGA_BIN1(uint32_t, 15, 0);
-            else if (e1_32) HGA_BIN1(uint32_t, 0, 0);
-            else if (kp.k == 21) HGA_BIN1(uint64_t, 21, 0);
-            else HGA_BIN1(uint64_t, 0, 0);
+            if (P > 1) {   // key-range passes: the same k variants, shifts from kp
+                if (e1_32 && kp.k == 19) HGA_BIN1(uint32_t, 19, 0, true);
+                else if (e1_32 && kp.k == 17) HGA_BIN1(uint32_t, 17, 0, true);
+                else if (e1_32 && kp.k == 15) HGA_BIN1(uint32_t, 15, 0, true);
+                else if (e1_32) HGA_BIN1(uint32_t, 0, 0, true);
+                else if (kp.k == 21) HGA_BIN1(uint64_t, 21, 0, true);
+                else HGA_BIN1(uint64_t, 0, 0, true);
+            }
+            else if (e1_32 && kp.k == 19 && kp.fb == MAX_FB && !HGA_B1_NOFB) HGA_BIN1(uint32_t, 19, MAX_FB, false);
+            else if (e1_32 && kp.k == 19) HGA_BIN1(uint32_t, 19, 0, false);
+            else if (e1_32 && kp.k == 17) HGA_BIN1(uint32_t, 17, 0, false);
+            else if (e1_32 && kp.k == 15) HGA_BIN1(uint32_t, 15, 0, false);
+            else if (e1_32) HGA_BIN1(uint32_t, 0, 0, false);
+            else if (kp.k == 21) HGA_BIN1(uint64_t, 21, 0, false);
+            else HGA_BIN1(uint64_t, 0, 0, false);
 #undef HGA_BIN1
         });
         c->check_launch("kc_bin1");
@@ -2564,41 +2718,44 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
         });
         c->check_launch("kc_fs");
     }
+    // a pass whose key range is heavier than `binned` holds: error bit, every bucket run emptied
+    if (P > 1) {
+        const uint64_t n_fs = (uint64_t)nb * (F + 1);
+        c->launch("kc_layout", [&] {
+            hipLaunchKernelGGL(kc_pass_guard, dim3(1), dim3(64), 0, c->stream, fs, n_fs, pl.binned_cap, gstat);
+            hipLaunchKernelGGL(kc_pass_void, dim3(blocks_for(n_fs, 256)), dim3(256), 0, c->stream, fs, n_fs, gstat);
+        });
+        c->check_launch("kc_pass_guard");
+    }
     // B2: re-bin every level-1 block into the fine buckets: one workgroup per first block and, behind
     // them in the same launch, a small grid over the spill blocks
     const unsigned spill_grid = (unsigned)std::min<uint64_t>(table_cap - n_first, HGA_SPILL_GRID);
     c->launch("kc_rebin", [&] {
-#define HGA_REBIN(E1T, ET)                                                                                 \
-    hipLaunchKernelGGL((kc_rebin<E1T, ET>), dim3((unsigned)n_first + spill_grid), dim3(rebin_nt<ET>()), 0,  \
+#define HGA_REBIN(E1T, ET, CL)                                                                                 \
+    hipLaunchKernelGGL((kc_rebin<E1T, ET, CL>), dim3((unsigned)n_first + spill_grid), dim3(rebin_nt<ET>()), 0,  \
                        c->stream, static_cast<const E1T*>(binned1), table, gstat, W, kp, nblk, off,        \
                        static_cast<ET*>(binned))
-        if (e1_32 && e32) HGA_REBIN(uint32_t, uint32_t);
-        else if (e32) HGA_REBIN(uint64_t, uint32_t);
-        else if (e1_32) HGA_REBIN(uint32_t, uint64_t);
-        else HGA_REBIN(uint64_t, uint64_t);
+        if (P > 1) {
+            if (e1_32 && e32) HGA_REBIN(uint32_t, uint32_t, true);
+            else if (e32) HGA_REBIN(uint64_t, uint32_t, true);
+            else if (e1_32) HGA_REBIN(uint32_t, uint64_t, true);
+            else HGA_REBIN(uint64_t, uint64_t, true);
+        }
+        else if (e1_32 && e32) HGA_REBIN(uint32_t, uint32_t, false);
+        else if (e32) HGA_REBIN(uint64_t, uint32_t, false);
+        else if (e1_32) HGA_REBIN(uint32_t, uint64_t, false);
+        else HGA_REBIN(uint64_t, uint64_t, false);
 #undef HGA_REBIN
     });
     c->check_launch("kc_rebin");
     // B3: one more split level for inputs whose fine buckets hold far more than one LDS table
-    // (the per-bucket estimate, total bytes >> fb, passes 2 x per_bucket only with fb at MAX_FB)
-    uint32_t fb3 = 0;
-    {
-        const uint64_t avg = total_bytes >> fb;
-        const char* te = std::getenv("HGA_SPLIT3_TARGET");
-        const char* fe = std::getenv("HGA_SPLIT3_FORCE");   // tests: split small inputs too
-        const uint64_t target = te ? std::strtoull(te, nullptr, 10) : 32768;
-        if (fe) {
-            const uint32_t want = (uint32_t)std::atoi(fe);
-            while (fb3 < want && fb3 < 8 && ((2u << fb3) * F) <= MAX_SF3 && kp.rbits - fb3 > 1) ++fb3;
-        } else if (avg > 2 * per_bucket && fb == MAX_FB) {
-            while (fb3 < 8 && (avg >> fb3) > target && ((2u << fb3) * F) <= MAX_SF3 && kp.rbits - fb3 > 10) ++fb3;
-        }
-    }
+    // (the per-bucket estimate, a pass's instances >> fb, passes 2 x per_bucket only with fb at MAX_FB)
+    const uint32_t fb3 = pl.fb3;
+    (void)per_bucket;
     if (fb3) {
-        const uint32_t S = 1u << fb3;
         // output regions: 1.25x every bucket + SLACK_3 per sub-bucket (kc_split3's slabs)
-        void* binned3 = s.binned3.ensure((total_bytes + total_bytes / 4 + (uint64_t)nb * S * SLACK_3 + 64) * esz);
-        uint64_t* fs3 = static_cast<uint64_t*>(s.file_start3.ensure((size_t)nb * S * (F + 1) * 8));
+        void* binned3 = binned3_buf;
+        uint64_t* fs3 = fs3_buf;
         c->launch("kc_split3", [&] {
             if (e32)
                 hipLaunchKernelGGL(kc_split3<uint32_t>, dim3(nb), dim3(NT_3), 0, c->stream,
@@ -2666,16 +2823,16 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     // the dense rows (an emitting count writes none: count_dense allocates them if a query needs them;
     // at a C4 rank shard's min-1 capacity they would be 60 GB)
     if (!d_xe) {
-        s.rows_key.ensure(cap * 8);
-        s.rows_cnt.ensure(cap * 4 * F);
+        s.rows_key.ensure(pl.b_rows_key);
+        s.rows_cnt.ensure(pl.b_rows_cnt);
     }
     // C: per-bucket count
     if (packed && e32) {
-        uint32_t* blist = static_cast<uint32_t*>(s.blist.ensure((size_t)nbc * 4));
+        uint32_t* blist = static_cast<uint32_t*>(s.blist.ensure(pl.b_blist));
         c->launch("kc_count", [&] {
             // instances per count bucket: >= 32 K (C2-sized) -> the lazy claim (HGA_CS_LAZY=0/1 forces)
             const char* le = std::getenv("HGA_CS_LAZY");
-            const bool lazy = le ? std::atoi(le) != 0 : (total_bytes >> kp.fb) >= 32768;
+            const bool lazy = le ? std::atoi(le) != 0 : (pass_bytes >> kp.fb) >= 32768;
             if (lazy)
                 hipLaunchKernelGGL(kc_count_s<true>, dim3(nbc), dim3(NT_P), 0, c->stream,
                                    static_cast<const uint32_t*>(binned), fs, F, min_per_file, kp,
@@ -2703,6 +2860,7 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
                                s.rows_key.as<uint64_t>(), s.rows_cnt.as<uint32_t>(), cap, gstat, (const uint32_t*)nullptr);
     });
     c->check_launch("kc_count");
+    }   // (passes)
     // No synchronisation here: the counters stay on the device until the next call that needs
     // them (count_settle), so the following spec_hist queues behind the count without a gap.
     s.rows_cap = cap;
@@ -2711,7 +2869,9 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     s.n_sel = 0;
     s.sel_rep_n = ~0ull;
     s.pending = true;
-    if (dumps) count_settle(c);   // the cached rows are merged on the host side now
+    bool any_dumps = false;
+    for (auto& v : s.dump_keys) any_dumps = any_dumps || !v.empty();
+    if (any_dumps) count_settle(c);   // the cached rows are merged on the host side now
 }
 
 // Read back the counters of a count_run that has not been settled yet (one D2H + sync, or the
@@ -2725,9 +2885,35 @@ void count_settle(hga_ctx* c, const unsigned long long* h) {
         c->sync();
         h = h_stat;
     }
+    // key-range passes: the instances of each (kc_pass_next's running sums; the last from the total)
+    const uint32_t P = s.run_passes;
+    s.pass_max = s.pass_min = h[4];
+    if (P > 1) {
+        std::vector<unsigned long long> cum(P, 0ull);
+        HGA_HIP(hipMemcpyAsync(cum.data(), s.pass_cum.p, (size_t)(P - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        cum[P - 1] = h[4];
+        s.pass_max = 0;
+        s.pass_min = ~0ull;
+        for (uint32_t p = 0; p < P; ++p) {
+            const uint64_t n = cum[p] - (p ? cum[p - 1] : 0ull);
+            s.pass_max = std::max<uint64_t>(s.pass_max, n);
+            s.pass_min = std::min<uint64_t>(s.pass_min, n);
+        }
+    }
     s.pending = false;
-    if (h[2] & 7ull) s.ran = false;   // a failed run has no rows to consume
-    s.last_err = h[2] & 7ull;         // proto::QE_UNSPLIT / QE_ROWCAP / QE_POOL
+    if (h[2] & 15ull) s.ran = false;   // a failed run has no rows to consume
+    // proto::QE_UNSPLIT / QE_ROWCAP / QE_POOL (a pass too heavy for `binned`, bit 8, reports as the pool does)
+    s.last_err = (h[2] & 7ull) | ((h[2] & 8ull) ? 4ull : 0ull);
+    if (P > 1 && (h[2] & 12ull)) {
+        // more passes do not split one key (or few): a key range far above its share needs a larger
+        // budget (the margin grows with it) or fewer passes
+        const std::string b = s.run_budget ? std::to_string(s.run_budget) + " bytes" : std::string("none set");
+        throw Error(HGA_ERR_OOM, std::string("a key range holds more than its pass's buffers (") +
+                                     ((h[2] & 4ull) ? "level-1 block pool" : "binned elements") + "): passes = " +
+                                     std::to_string(P) + ", budget = " + b +
+                                     "; give hga_count_set_passes a larger budget or fewer passes");
+    }
     HGA_REQUIRE(!(h[2] & 4ull), HGA_ERR_OOM, "level-1 block pool exhausted");
     HGA_REQUIRE(!(h[2] & 1ull), HGA_ERR_INVALID, "a bucket could not be split to fit the LDS table");
     HGA_REQUIRE(!(h[2] & 2ull), HGA_ERR_OOM, "row capacity exceeded");

@@ -173,6 +173,11 @@ struct CountState {
     uint64_t xb_cap = 0;             // rows_key / rows_cnt capacity of that run
     bool dense_pending = false;      // rows_key / rows_cnt not written yet (count_dense)
     bool pending = false;   // count_run's counters not read back yet (count_settle)
+    // key-range passes (hga_count_set_passes; count_sizing.hpp): the configured passes (0: chosen from
+    // the budget) and budget (0: none), and what the last run used / its settle found
+    uint32_t cfg_passes = 0, run_passes = 1;
+    uint64_t cfg_budget = 0, run_budget = 0, work_bytes = 0, pass_max = 0, pass_min = 0;
+    DevBuf pass_cum;   // instances of passes 0..p (P - 1 running sums, kc_pass_next)
     bool dist = false;      // rows are this rank's owner range after hga_count_exchange
     ~CountState() {
         for (auto* b : seq) delete b;
@@ -294,6 +299,7 @@ struct hga_ctx {
         return side;
     }
     int num_cu = 256;
+    uint64_t total_mem = ~0ull;   // device memory (hga_ctx_create)
     hga::Profiler prof;
     hga::CountState count;
     hga::LookupState lookup;
@@ -354,6 +360,9 @@ namespace hga {
 void count_begin(hga_ctx* c, int k, uint32_t n_files);
 void count_add(hga_ctx* c, uint32_t file, const char* seq, uint64_t n);
 void count_run(hga_ctx* c, uint32_t min_per_file);
+// key-range passes (count.hip): the setting, and the bytes count_run would request under it
+void count_set_passes(hga_ctx* c, uint32_t passes, uint64_t budget);
+uint64_t count_estimate(hga_ctx* c, uint32_t min_per_file, uint32_t passes);
 // before_publish (optional): called once the histogram's (threshold << 56 | total, count) pairs are
 // compacted on the device (ctrl[0] overflow rows, ctrl[2] pairs), before the call's one
 // synchronisation — the multi-GPU gather enqueues its collective there

@@ -35,6 +35,11 @@ class CountStats(C.Structure):
                 ("buckets", C.c_uint32), ("max_split", C.c_uint32)]
 
 
+class CountPassStats(C.Structure):   # hga_count_pass_stats
+    _fields_ = [("passes", C.c_uint32), ("pad", C.c_uint32), ("work_bytes", C.c_uint64),
+                ("max_pass_instances", C.c_uint64), ("min_pass_instances", C.c_uint64)]
+
+
 class LookupSizes(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("windows", C.c_uint64), ("hits", C.c_uint64),
                 ("firsts", C.c_uint64), ("reads_hit", C.c_uint64), ("n_sdk", C.c_uint32)]
@@ -84,6 +89,9 @@ HGA_SYMBOLS = {
     "hga_count_add_rows": (C.c_int, [_vp, C.c_uint32, _u64p, _u32p, C.c_uint64]),
     "hga_count_run": (C.c_int, [_vp, C.c_uint32]),
     "hga_count_get_stats": (C.c_int, [_vp, C.POINTER(CountStats)]),
+    "hga_count_set_passes": (C.c_int, [_vp, C.c_uint32, C.c_uint64]),
+    "hga_count_estimate": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u64p]),
+    "hga_count_get_pass_stats": (C.c_int, [_vp, C.POINTER(CountPassStats)]),
     "hga_count_spec_hist": (C.c_int, [_vp, C.POINTER(C.c_double), C.c_uint32, C.POINTER(_i64p), _u64p]),
     "hga_count_select": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(_u64p), _u64p, _u64p]),
     "hga_count_select_ex": (C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(_u64p), C.POINTER(_u8p), _u64p,
@@ -332,6 +340,22 @@ class Ctx:
     def count_stats(self) -> CountStats:
         s = CountStats()
         _ck(lib().hga_count_get_stats(self._h, C.byref(s)))
+        return s
+
+    def count_set_passes(self, passes: int = 0, budget: int = 0):
+        """Key-range passes of the following count_run calls: `passes` (0: chosen from `budget`),
+        `budget` = device bytes the work buffers and rows may use (0: the free device memory)."""
+        _ck(lib().hga_count_set_passes(self._h, passes, budget))
+
+    def count_estimate(self, min_count: int, passes: int) -> int:
+        """Bytes count_run(min_count) would request at `passes` for what has been added (host arithmetic)."""
+        b = C.c_uint64()
+        _ck(lib().hga_count_estimate(self._h, min_count, passes, C.byref(b)))
+        return b.value
+
+    def count_pass_stats(self) -> CountPassStats:
+        s = CountPassStats()
+        _ck(lib().hga_count_get_pass_stats(self._h, C.byref(s)))
         return s
 
     def spec_hist(self, thresholds):

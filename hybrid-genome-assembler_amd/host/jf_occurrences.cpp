@@ -65,6 +65,20 @@ using hgah::PhaseTimer;
 
 using KmerSpecificity = std::map<double, std::map<int, int>>;
 
+// "--mem-budget": bytes, with an optional K / M / G suffix (powers of 1024)
+uint64_t parse_bytes(const std::string& v) {
+    size_t pos = 0;
+    const unsigned long long n = std::stoull(v, &pos);
+    unsigned shift = 0;
+    if (pos < v.size()) {
+        const char u = v[pos];
+        shift = u == 'K' || u == 'k' ? 10 : u == 'M' || u == 'm' ? 20 : u == 'G' || u == 'g' ? 30 : 64;
+        if (shift == 64 || pos + 1 != v.size() || (n >> (64 - shift)) != 0)
+            throw std::invalid_argument("the argument ('" + v + "') for option '--mem-budget' is invalid");
+    }
+    return (uint64_t)n << shift;
+}
+
 // plot_kmer_specificity (src/common/Plotting.cpp:20-37)
 std::string plot_wire(const std::map<int, KmerSpecificity>& specs, int max_coverage) {
     std::string ks;
@@ -106,6 +120,13 @@ int main(int argc, char* argv[]) {
     int gpus = 1;
     ap.add("gpus", 0, false, "GPUs to count on, one rank each (MI355X build extension; default 1)",
            [&](const std::string& v) { gpus = std::stoi(v); });
+    // counting in key-range passes (hga_count_set_passes): without either option the library chooses
+    uint32_t passes = 0;
+    uint64_t mem_budget = 0;
+    ap.add("passes", 0, false, "Count in this many key-range passes (MI355X build extension; default: as many as the memory needs)",
+           [&](const std::string& v) { passes = (uint32_t)std::stoul(v); });
+    ap.add("mem-budget", 0, false, "Device bytes the count may use, suffix K/M/G (MI355X build extension; default: the free memory)",
+           [&](const std::string& v) { mem_budget = parse_bytes(v); });
     ap.parse(argc, argv);
     for (auto& p : ap.positional) read_paths.push_back(p);
     if (ap.has("help")) {
@@ -182,13 +203,20 @@ int main(int argc, char* argv[]) {
     }
     tm.mark("upload");
     if (P == 1) {
+        if (ap.has("passes") || ap.has("mem-budget"))
+            check(hga_count_set_passes(ctx, passes, mem_budget), "hga_count_set_passes");
         check(hga_count_run(ctx, 2), "hga_count_run");   // jellyfish --bc: per-file singletons dropped
         if (tm.on) {   // (the count is asynchronous; the stats wait for it)
             hga_count_stats st;
             check(hga_count_get_stats(ctx, &st), "hga_count_get_stats");
             tm.mark("count");
+            hga_count_pass_stats ps;
+            check(hga_count_get_pass_stats(ctx, &ps), "hga_count_get_pass_stats");
+            std::fprintf(stderr, "hga-timing count.passes %u\n", ps.passes);
         }
     } else {
+        if (ap.has("passes") || ap.has("mem-budget"))
+            throw std::invalid_argument("--passes / --mem-budget count on one GPU; they cannot be combined with --gpus");
         ranks.each([](int, hga_ctx* c) {
             check(hga_count_run(c, 1), "hga_count_run");   // no drop before the global sum
             check(hga_count_exchange(c, 2), "hga_count_exchange");

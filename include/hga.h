@@ -96,6 +96,36 @@ typedef struct hga_count_stats {
 } hga_count_stats;
 hga_status hga_count_get_stats(hga_ctx* ctx, hga_count_stats* out);
 
+/* Key-range passes: inputs whose work buffers would not fit the device are counted in P passes,
+ * each a complete count of the keys whose hashed value starts with the pass's log2 P bits, in
+ * buffers of about 1/P of the size; the reads stay resident (1 B/base) and are read P times.  The
+ * results (rows, dumps, histogram, export) are those of one pass.
+ * passes: 0 = choose from budget_bytes; >= 1 = exactly that many (rounded up to a power of two, clamped
+ * to 256 and to what k allows: 2k - log2 P >= 7, two passes at most for k <= 3).
+ * budget_bytes: device bytes the count's work buffers and rows may use; 0 = free device memory at
+ * hga_count_run (hipMemGetInfo) less a margin.  Default (never called): as today when one pass fits
+ * the free memory, else the smallest P that does.
+ * A pass's buffers hold 1.25x its expected share of the instances; with budget_bytes > 0 that margin
+ * grows as far as the budget allows, up to the whole input.  A key range heavier than that (one k-mer
+ * that is a large share of the input: more passes do not split a key) makes the next consuming call
+ * fail with HGA_ERR_OOM, the text naming passes and budget; so does a request that cannot fit
+ * budget_bytes at any P (at hga_count_run).  When the rows' full capacity (bases / min_per_file) does
+ * not fit, they get what the budget leaves (row capacity exceeded -> HGA_ERR_OOM as ever).
+ * Not supported on a ctx with a communicator: hga_count_run with P > 1 returns HGA_ERR_STATE. */
+hga_status hga_count_set_passes(hga_ctx* ctx, uint32_t passes, uint64_t budget_bytes);
+/* Host arithmetic only: the bytes hga_count_run would request for everything added so far, at
+ * `passes` (0: the P the budget set by hga_count_set_passes chooses; one pass without a budget) under
+ * that budget.  The scans' scratch (a few KB) is not included. */
+hga_status hga_count_estimate(hga_ctx* ctx, uint32_t min_per_file, uint32_t passes, uint64_t* bytes);
+typedef struct hga_count_pass_stats {
+    uint32_t passes;            /* passes the last run used (after clamping)            */
+    uint32_t pad;
+    uint64_t work_bytes;        /* bytes the run requested for work buffers + rows      */
+    uint64_t max_pass_instances;
+    uint64_t min_pass_instances;
+} hga_count_pass_stats;
+hga_status hga_count_get_pass_stats(hga_ctx* ctx, hga_count_pass_stats* out);
+
 /* Specificity histogram — JellyfishOccurrenceReader::get_specificity
  * (src/occurrences/JellyfishOccurrenceReader.cpp:88-108): for every merged row,
  * spec = first threshold > ((double)max_f c_f / (double)Σ c_f) * 100 and
