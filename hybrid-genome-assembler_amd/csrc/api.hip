@@ -46,6 +46,12 @@ T* host_dup(const T* src, size_t n) {
     if (n) std::memcpy(p, src, n * sizeof(T));
     return p;
 }
+
+// Between hga_lookup_begin and hga_lookup_finish there is no lookup result and no resident read set.
+void no_session(hga_ctx* c, const char* fn) {
+    HGA_REQUIRE(!c->lookup.batch.open, HGA_ERR_STATE,
+                std::string(fn) + ": a read-batch session is open (hga_lookup_begin without hga_lookup_finish)");
+}
 }  // namespace
 
 #define HGA_CTX_GUARD(c, ...)                               \
@@ -56,6 +62,8 @@ T* host_dup(const T* src, size_t n) {
             __VA_ARGS__;                                    \
         });                                                 \
     } while (0)
+// the same for a call that reads a lookup result or the resident reads: not inside a read-batch session
+#define HGA_RESULT_GUARD(c, fn, ...) HGA_CTX_GUARD(c, { no_session(c, fn); __VA_ARGS__; })
 
 extern "C" {
 
@@ -127,7 +135,7 @@ hga_status hga_count_add(hga_ctx* c, uint32_t file, const char* seq, uint64_t n_
 
 hga_status hga_connections_run(hga_ctx* c, const uint32_t* pivots, uint64_t n_pivots, uint32_t min_kmers,
                                uint64_t min_score, const int32_t* categories, uint64_t* n) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_connections_run", {
         HGA_REQUIRE(n, HGA_ERR_INVALID, "null out pointer");
         HGA_REQUIRE(pivots || n_pivots == 0, HGA_ERR_INVALID, "null pivots with n_pivots > 0");
         hga::connections_run(c, pivots, n_pivots, min_kmers, min_score, categories, n);
@@ -145,16 +153,16 @@ hga_status hga_connections_fetch_range(hga_ctx* c, uint64_t first, uint64_t coun
 
 hga_status hga_read_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap,
                              uint32_t* shared) {
-    HGA_CTX_GUARD(c, hga::read_overlaps(c, x, y, n, overlap, shared));
+    HGA_RESULT_GUARD(c, "hga_read_overlaps", hga::read_overlaps(c, x, y, n, overlap, shared));
 }
 
 hga_status hga_components_merge(hga_ctx* c, const uint64_t* group_ptr, const uint32_t* ids, uint64_t n_groups) {
-    HGA_CTX_GUARD(c, hga::components_merge(c, group_ptr, ids, n_groups));
+    HGA_RESULT_GUARD(c, "hga_components_merge", hga::components_merge(c, group_ptr, ids, n_groups));
 }
 
 hga_status hga_components_connections(hga_ctx* c, const uint32_t* pivots, uint64_t n_pivots, uint64_t min_score,
                                       uint64_t* n) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_components_connections", {
         HGA_REQUIRE(n, HGA_ERR_INVALID, "null out pointer");
         HGA_REQUIRE(pivots || n_pivots == 0, HGA_ERR_INVALID, "null pivots with n_pivots > 0");
         hga::components_connections(c, pivots, n_pivots, min_score, n);
@@ -163,25 +171,25 @@ hga_status hga_components_connections(hga_ctx* c, const uint32_t* pivots, uint64
 
 hga_status hga_components_overlaps(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, int32_t* overlap,
                                    uint32_t* shared) {
-    HGA_CTX_GUARD(c, hga::components_overlaps(c, x, y, n, overlap, shared));
+    HGA_RESULT_GUARD(c, "hga_components_overlaps", hga::components_overlaps(c, x, y, n, overlap, shared));
 }
 
 hga_status hga_tree_tails(hga_ctx* c, const uint64_t* tree_ptr, const uint32_t* ex, const uint32_t* ey, uint64_t n_trees,
                           const int32_t* overlap, const uint32_t* read_length, uint64_t tail_length, uint64_t* left_ptr,
                           uint32_t* left, uint64_t* right_ptr, uint32_t* right, hga_tree_ends* ends) {
-    HGA_CTX_GUARD(c, hga::tree_tails(c, tree_ptr, ex, ey, n_trees, overlap, read_length, tail_length, left_ptr, left,
+    HGA_RESULT_GUARD(c, "hga_tree_tails", hga::tree_tails(c, tree_ptr, ex, ey, n_trees, overlap, read_length, tail_length, left_ptr, left,
                                      right_ptr, right, ends));
 }
 
 hga_status hga_spanning_forest(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first, uint64_t count,
                                uint64_t* n_edges) {
-    HGA_CTX_GUARD(c, hga::spanning_forest(c, x, y, n, first, count, n_edges));
+    HGA_RESULT_GUARD(c, "hga_spanning_forest", hga::spanning_forest(c, x, y, n, first, count, n_edges));
 }
 
 hga_status hga_spanning_forest_restricted(hga_ctx* c, const uint32_t* x, const uint32_t* y, uint64_t n, uint64_t first,
                                           uint64_t count, const uint32_t* restricted, uint64_t n_restricted,
                                           uint64_t* n_edges) {
-    HGA_CTX_GUARD(c, hga::spanning_forest_restricted(c, x, y, n, first, count, restricted, n_restricted, n_edges));
+    HGA_RESULT_GUARD(c, "hga_spanning_forest_restricted", hga::spanning_forest_restricted(c, x, y, n, first, count, restricted, n_restricted, n_edges));
 }
 
 hga_status hga_spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uint32_t* y) {
@@ -191,7 +199,7 @@ hga_status hga_spanning_forest_fetch(hga_ctx* c, uint64_t* pos, uint32_t* x, uin
 hga_status hga_connections_quality(hga_ctx* c, const uint32_t* x, const uint32_t* y, const uint64_t* score,
                                    const uint8_t* is_good, uint64_t n, int per_candidate, const int32_t* vertex_class,
                                    uint64_t** out_score, uint64_t** out_good, uint64_t** out_bad, uint64_t* n_rows) {
-    HGA_CTX_GUARD(c, hga::connections_quality(c, x, y, score, is_good, n, per_candidate, vertex_class, out_score, out_good,
+    HGA_RESULT_GUARD(c, "hga_connections_quality", hga::connections_quality(c, x, y, score, is_good, n, per_candidate, vertex_class, out_score, out_good,
                                               out_bad, n_rows));
 }
 
@@ -200,29 +208,29 @@ uint32_t hga_connections_quality_tile(void) { return hga::connections_quality_ti
 hga_status hga_components_set_scores(hga_ctx* c, const uint64_t* set_ptr, const uint32_t* ids, uint64_t n_sets,
                                      const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint64_t* score,
                                      uint64_t* set_size) {
-    HGA_CTX_GUARD(c, hga::components_set_scores(c, set_ptr, ids, n_sets, pair_a, pair_b, n_pairs, score, set_size));
+    HGA_RESULT_GUARD(c, "hga_components_set_scores", hga::components_set_scores(c, set_ptr, ids, n_sets, pair_a, pair_b, n_pairs, score, set_size));
 }
 
 hga_status hga_components_get_sizes(hga_ctx* c, hga_components_sizes* out) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_components_get_sizes", {
         HGA_REQUIRE(out, HGA_ERR_INVALID, "null out pointer");
         hga::components_sizes(c, out);
     });
 }
 
 hga_status hga_components_fetch_index(hga_ctx* c, uint64_t* ptr, uint32_t* ids) {
-    HGA_CTX_GUARD(c, hga::components_fetch_index(c, ptr, ids));
+    HGA_RESULT_GUARD(c, "hga_components_fetch_index", hga::components_fetch_index(c, ptr, ids));
 }
 
 hga_status hga_components_fetch_kmers(hga_ctx* c, uint32_t id, uint32_t* kmers, uint64_t* n) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_components_fetch_kmers", {
         HGA_REQUIRE(n, HGA_ERR_INVALID, "null out pointer");
         hga::components_fetch_kmers(c, id, kmers, n);
     });
 }
 
 hga_status hga_components_reset(hga_ctx* c) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_components_reset", {
         HGA_REQUIRE(c->lookup.ran, HGA_ERR_STATE, "hga_lookup_run not called");
         hga::components_drop(c);
     });
@@ -426,7 +434,7 @@ hga_status hga_count_dump(hga_ctx* c, uint32_t file, uint64_t** keys, uint32_t**
 }
 
 hga_status hga_lookup_load(hga_ctx* c, int k, const uint64_t* keys, uint32_t n) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_lookup_load", {
         HGA_REQUIRE(keys || n == 0, HGA_ERR_INVALID, "null keys");
         hga::components_drop(c);
         hga::lookup_load(c, k, keys, n);
@@ -444,28 +452,63 @@ hga_status hga_lookup_set_reads(hga_ctx* c, const char* bases, const uint64_t* o
 }
 
 hga_status hga_lookup_run(hga_ctx* c) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_lookup_run", {
         hga::components_drop(c);
         hga::lookup_run(c);
     });
 }
 
 hga_status hga_lookup_get_sizes(hga_ctx* c, hga_lookup_sizes* out) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_lookup_get_sizes", {
         HGA_REQUIRE(out, HGA_ERR_INVALID, "null out pointer");
         hga::lookup_sizes(c, out);
     });
 }
 
 hga_status hga_lookup_fetch(hga_ctx* c, const hga_lookup_result* out) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_lookup_fetch", {
         HGA_REQUIRE(out, HGA_ERR_INVALID, "null out pointer");
         hga::lookup_fetch(c, out);
     });
 }
 
-hga_status hga_hll_registers(hga_ctx* c, int k, uint32_t b, uint8_t* registers) {
+hga_status hga_lookup_begin(hga_ctx* c, uint32_t first_read_id) {
     HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(c->lookup.loaded, HGA_ERR_STATE, "hga_lookup_load not called");
+        hga::components_drop(c);
+        hga::lookup_begin(c, first_read_id);
+    });
+}
+
+hga_status hga_lookup_add_reads(hga_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n_reads) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(offsets, HGA_ERR_INVALID, "null offsets");
+        HGA_REQUIRE(bases || offsets[n_reads] == 0, HGA_ERR_INVALID, "null bases");
+        hga::lookup_add_reads(c, bases, offsets, n_reads);
+    });
+}
+
+hga_status hga_lookup_finish(hga_ctx* c) {
+    HGA_CTX_GUARD(c, hga::lookup_finish(c));
+}
+
+hga_status hga_lookup_batch_estimate(hga_ctx* c, uint64_t batch_bases, uint64_t batch_reads, uint64_t* slot_bytes) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(slot_bytes, HGA_ERR_INVALID, "null out pointer");
+        *slot_bytes = hga::lookup_batch_estimate(batch_bases, batch_reads);
+    });
+}
+
+hga_status hga_lookup_get_batch_stats(hga_ctx* c, hga_lookup_batch_stats* out) {
+    HGA_CTX_GUARD(c, {
+        HGA_REQUIRE(out, HGA_ERR_INVALID, "null out pointer");
+        HGA_REQUIRE(c->lookup.batch.ever, HGA_ERR_STATE, "hga_lookup_begin not called");
+        *out = c->lookup.batch.stats;
+    });
+}
+
+hga_status hga_hll_registers(hga_ctx* c, int k, uint32_t b, uint8_t* registers) {
+    HGA_RESULT_GUARD(c, "hga_hll_registers", {
         HGA_REQUIRE(registers, HGA_ERR_INVALID, "null registers");
         hga::hll_registers(c, k, (int)b, registers);
     });
@@ -547,7 +590,7 @@ hga_status hga_count_exchange(hga_ctx* c, uint32_t min_per_file) {
 }
 
 hga_status hga_lookup_gather(hga_ctx* c) {
-    HGA_CTX_GUARD(c, {
+    HGA_RESULT_GUARD(c, "hga_lookup_gather", {
         hga::components_drop(c);
         hga::lookup_gather(c);
     });

@@ -59,6 +59,28 @@ struct DevBuf {
         cap = b;
         return p;
     }
+    // The keep-variant of ensure: a larger allocation whose first keep_bytes are copied from the old one on
+    // stream s.  The old allocation is handed to `old` (empty before the call) instead of being freed: the
+    // copy is only enqueued, so the caller frees it once the stream has passed the copy.  Returns true
+    // when it grew.
+    bool grow_keep(size_t bytes, size_t keep_bytes, hipStream_t s, DevBuf& old) {
+        if (bytes <= cap && p) return false;
+        void* np = nullptr;
+        const size_t b = bytes ? bytes : 16;
+        HGA_HIP(hipMalloc(&np, b));
+        if (p && keep_bytes) {
+            const hipError_t e = hipMemcpyAsync(np, p, keep_bytes, hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) {
+                (void)hipFree(np);
+                HGA_HIP(e);
+            }
+        }
+        old.p = p;
+        old.cap = cap;
+        p = np;
+        cap = b;
+        return true;
+    }
     template <class T>
     T* as() const { return static_cast<T*>(p); }
 };
@@ -206,6 +228,40 @@ struct LookupState {
     bool gathered = false;
     uint64_t loc_n_reads = 0;
     uint32_t loc_first_read_id = 1;
+    // read batches (hga_lookup_begin / _add_reads / _finish; lookup.hip, sizes in lookup_sizing.hpp)
+    struct BatchSlot {
+        DevBuf dev;            // one allocation cut by lksizing::slot
+        PinnedBuf stage;       // the upload's host side: bases, then offsets
+        uint64_t cap_bases = 0, cap_reads = 0;   // the batch size `dev` / `stage` were cut for
+        PinnedBuf h_hits;      // the batch's hit count, copied behind its count scan
+        hipEvent_t ev_up = nullptr, ev_cnt = nullptr, ev_free = nullptr;   // uploaded; counted; last reader done
+        bool used = false;     // ev_free has been recorded
+    };
+    struct Batch {
+        bool open = false, ever = false;   // a session is open; one was begun on this ctx
+        BatchSlot slot[2];
+        uint64_t next = 0;     // batches that took a slot so far (slot = next & 1)
+        // the batch whose count scan is enqueued and whose emit is not: its slot, sizes and bases
+        bool pending = false;
+        int p_slot = 0;
+        uint64_t p_reads = 0, p_bases = 0, p_read_base = 0, p_tiles = 0;
+        uint64_t hits = 0;     // hits appended (emitted) so far
+        uint64_t slot_max_bases = 0, slot_max_reads = 0;
+        // hit arrays replaced by a larger copy, freed once `ev` (recorded behind the copies) has passed
+        struct Retired {
+            DevBuf buf[5];
+            hipEvent_t ev = nullptr;
+        };
+        std::vector<std::unique_ptr<Retired>> retired;
+        hga_lookup_batch_stats stats = {};
+    } batch;
+    ~LookupState() {
+        for (auto& s : batch.slot)
+            for (hipEvent_t e : {s.ev_up, s.ev_cnt, s.ev_free})
+                if (e) (void)hipEventDestroy(e);
+        for (auto& r : batch.retired)
+            if (r->ev) (void)hipEventDestroy(r->ev);
+    }
 };
 
 struct ConnState {
@@ -464,6 +520,12 @@ void lookup_load(hga_ctx* c, int k, const uint64_t* keys, uint32_t n);
 void lookup_set_reads(hga_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n,
                       uint32_t first_id);
 void lookup_run(hga_ctx* c);
+// read batches (lookup.hip): a session bounds the scan's device memory by the batch, not the read set
+void lookup_begin(hga_ctx* c, uint32_t first_id);
+void lookup_add_reads(hga_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n);
+void lookup_finish(hga_ctx* c);
+void lookup_abandon(hga_ctx* c);   // closes an open session, joining everything it enqueued
+uint64_t lookup_batch_estimate(uint64_t batch_bases, uint64_t batch_reads);
 void lookup_pack(hga_ctx* c, bool skip_codes = false);   // per-base encode of the resident reads (lookup_run, hll_registers)
 void lookup_sizes(hga_ctx* c, hga_lookup_sizes* out);
 void lookup_fetch(hga_ctx* c, const hga_lookup_result* out);

@@ -22,6 +22,7 @@
 
 #include "hga_internal.hpp"
 #include "kmer_dev.hpp"
+#include "lookup_sizing.hpp"
 
 namespace hga {
 namespace {
@@ -1264,6 +1265,7 @@ void lookup_set_reads(hga_ctx* c, const char* bases, const uint64_t* offsets, ui
     for (uint64_t i = 0; i < n; ++i)
         HGA_REQUIRE(offsets[i + 1] >= offsets[i], HGA_ERR_INVALID, "offsets must be non-decreasing");
     const uint64_t nb = n ? offsets[n] - offsets[0] : 0;
+    lookup_abandon(c);   // an open batch session ends here: back to the one-shot path
     L.gathered = false;
     L.n_reads = n;
     L.n_bases = nb;
@@ -1312,6 +1314,326 @@ void lookup_pack(hga_ctx* c, bool skip_codes) {
     L.packed_ok = !skip_codes;
 }
 
+// The count scan of n reads / nb bases (lk_scan<false, ...> picked by k and the table layout) on the ctx stream.
+static void lookup_count_scan(hga_ctx* c, uint64_t n_tiles, const uint32_t* pk, const uint16_t* vd, const unsigned int* sb,
+                              uint64_t nb, const uint64_t* offs, uint64_t n, const uint32_t* word_read, const LkTab& tab,
+                              uint32_t* hm, uint32_t* wkid, unsigned long long* tile) {
+    auto& L = c->lookup;
+    const int k = L.k;
+    c->launch("lk_count", [&] {
+#define HGA_LK_SCAN2(KMV, KK, PKV)                                                                           \
+    hipLaunchKernelGGL((lk_scan<false, KMV, KK, PKV>), dim3((unsigned)n_tiles), dim3(LK_T), 0, c->stream, pk, vd, \
+                       sb, nb, offs, n, k, word_read, tab, hm, wkid, tile, (uint32_t*)nullptr,                   \
+                       (uint32_t*)nullptr, (uint32_t*)nullptr)
+#define HGA_LK_SCAN(KMV, KK)                       \
+    do {                                           \
+        if (L.idb) HGA_LK_SCAN2(KMV, KK, true);    \
+        else HGA_LK_SCAN2(KMV, KK, false);         \
+    } while (0)
+        if (L.km == LK_KM && k == 19) HGA_LK_SCAN(LK_KM, 19);   // compile-time k for the usual SDK k
+        else if (L.km == LK_KM && k == 21) HGA_LK_SCAN(LK_KM, 21);
+        else if (L.km == LK_KM) HGA_LK_SCAN(LK_KM, 0);
+        else if (L.km == 6) HGA_LK_SCAN(6, 17);   // k = 17
+        else if (L.km == 5) HGA_LK_SCAN(5, 16);
+        else if (L.km == 4) HGA_LK_SCAN(4, 15);
+        else HGA_LK_SCAN(0, 0);
+#undef HGA_LK_SCAN
+#undef HGA_LK_SCAN2
+    });
+    c->check_launch("lk_count");
+}
+
+static void lookup_build_indices(hga_ctx* c, uint64_t n, uint64_t H);
+
+// ---- read batches (hga_lookup_begin / _add_reads / _finish) -------------------------------------------
+// A batch is scanned in a slot (lookup_sizing.hpp) with batch-local read indices and base positions, by the
+// kernels of the one-shot path; its hits are emitted behind the earlier batches' in hit_read / hit_kid /
+// hit_pos / s_key / s_val and lk_rebase then adds the reads before the batch to hit_read and to the read
+// bits of s_key.  hga_lookup_finish runs lookup_build_indices over all of them.
+//
+// Order on the streams, batch i in slot i & 1 (two slots):
+//   side stream   wait ev_free[slot] (emit of batch i - 2) -> upload i from the slot's pinned staging -> ev_up
+//   ctx stream    wait ev_up -> read map, count scan, tile scan, hit count to pinned memory -> ev_cnt
+//   host          waits ev_cnt of batch i - 1 (its one wait), grows the hit arrays, then on the ctx stream:
+//                 emit i - 1, rebase i - 1 -> ev_free[slot of i - 1]
+// so the GPU has batch i's count scan queued while the host reads batch i - 1's hit count, and the upload of
+// batch i overlaps the kernels of batch i - 1.  The pinned staging of a slot is rewritten by the host only
+// after the hit count of the batch that used it last has been read, which is behind its upload.
+namespace {
+__global__ void __launch_bounds__(256) lk_rebase(uint32_t* __restrict__ h_read, uint64_t* __restrict__ h_skey,
+                                                 uint64_t n, uint32_t read_base, int kbits) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    h_read[i] += read_base;
+    h_skey[i] += (uint64_t)read_base << kbits;
+}
+
+static_assert(lksizing::kP == LK_P && lksizing::kT == LK_T && lksizing::kSbPad == SB_PAD,
+              "lookup_sizing.hpp restates the scan's frame, tile and bitmap pad");
+
+void batch_events(LookupState::BatchSlot& s) {
+    for (hipEvent_t* e : {&s.ev_up, &s.ev_cnt, &s.ev_free})
+        if (!*e) HGA_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+}
+
+// Joins everything a session may have in flight: after this no kernel or copy reads a slot, the pinned
+// staging or a retired hit array.  Never throws (used on error paths and before buffers are freed).
+void batch_join(hga_ctx* c) {
+    if (c->side) (void)hipStreamSynchronize(c->side);
+    (void)hipStreamSynchronize(c->stream);
+    auto& B = c->lookup.batch;
+    for (auto& r : B.retired)
+        if (r->ev) (void)hipEventDestroy(r->ev);
+    B.retired.clear();   // (DevBuf frees)
+}
+
+// Frees the retired hit arrays whose copies the ctx stream has passed (no wait).
+void batch_reap(hga_ctx* c) {
+    auto& R = c->lookup.batch.retired;
+    for (size_t i = 0; i < R.size();) {
+        if (hipEventQuery(R[i]->ev) == hipSuccess) {
+            (void)hipEventDestroy(R[i]->ev);
+            R.erase(R.begin() + (long)i);
+        } else {
+            (void)hipGetLastError();   // "not ready" is no error of a launch: keep it out of check_launch
+            ++i;
+        }
+    }
+}
+
+// Room for `need` hits in the five appended arrays, the first `keep` kept.
+void batch_grow_hits(hga_ctx* c, uint64_t need, uint64_t keep) {
+    auto& L = c->lookup;
+    auto& B = L.batch;
+    DevBuf* arr[5] = {&L.hit_read, &L.hit_kid, &L.hit_pos, &L.s_key, &L.s_val};
+    const size_t esz[5] = {4, 4, 4, 8, 4};
+    uint64_t cap = ~0ull;
+    for (int a = 0; a < 5; ++a) cap = std::min<uint64_t>(cap, arr[a]->p ? arr[a]->cap / esz[a] : 0);
+    const uint64_t ncap = lksizing::grow_hits(cap, std::max<uint64_t>(need, 1));
+    if (ncap == cap) return;
+    auto ret = std::make_unique<LookupState::Batch::Retired>();
+    HGA_HIP(hipEventCreateWithFlags(&ret->ev, hipEventDisableTiming));
+    auto* rp = ret.get();
+    B.retired.push_back(std::move(ret));   // owned by the session from here: an error below frees nothing early
+    for (int a = 0; a < 5; ++a) arr[a]->grow_keep(ncap * esz[a], keep * esz[a], c->stream, rp->buf[a]);
+    HGA_HIP(hipEventRecord(rp->ev, c->stream));
+    if (keep) ++B.stats.regrowths;
+}
+
+// The pending batch: waits for its hit count, appends its hits (emit + rebase) and frees its slot.
+void batch_emit_pending(hga_ctx* c) {
+    auto& L = c->lookup;
+    auto& B = L.batch;
+    if (!B.pending) return;
+    auto& S = B.slot[B.p_slot];
+    HGA_HIP(hipEventSynchronize(S.ev_cnt));
+    ++B.stats.host_waits;
+    batch_reap(c);
+    const uint64_t H = *static_cast<const volatile unsigned long long*>(S.h_hits.p);
+    const lksizing::Slot z = lksizing::slot(S.cap_bases, S.cap_reads);
+    char* d = S.dev.as<char>();
+    if (H) {
+        batch_grow_hits(c, B.hits + H, B.hits);
+        const int kbits = bits_for(std::max<uint32_t>(L.n_sdk, 1));
+        uint32_t* hr = L.hit_read.as<uint32_t>() + B.hits;
+        uint32_t* hk = L.hit_kid.as<uint32_t>() + B.hits;
+        uint32_t* hp = L.hit_pos.as<uint32_t>() + B.hits;
+        uint64_t* sk = L.s_key.as<uint64_t>() + B.hits;
+        uint32_t* sv = L.s_val.as<uint32_t>() + B.hits;
+        LkTab tab{L.tab_key.p, L.filter.as<uint32_t>(), L.slots, L.fwords - 1, L.idb,
+                  reinterpret_cast<const uint8_t*>(d + z.o_bases)};
+        c->launch("lk_emit", [&] {
+            hipLaunchKernelGGL((lk_scan<true, 0>), dim3((unsigned)B.p_tiles), dim3(LK_T), 0, c->stream,
+                               (const uint32_t*)nullptr, (const uint16_t*)nullptr,
+                               reinterpret_cast<const unsigned int*>(d + z.o_starts), B.p_bases,
+                               reinterpret_cast<const uint64_t*>(d + z.o_offsets), B.p_reads, L.k,
+                               reinterpret_cast<const uint32_t*>(d + z.o_word_read), tab,
+                               reinterpret_cast<uint32_t*>(d + z.o_hmask), reinterpret_cast<uint32_t*>(d + z.o_win_kid),
+                               reinterpret_cast<unsigned long long*>(d + z.o_tile), hr, hk, hp, sk, sv, kbits);
+        });
+        c->check_launch("lk_emit");
+        if (B.p_read_base) {
+            c->launch("lk_rebase", [&] {
+                hipLaunchKernelGGL(lk_rebase, dim3(blocks_for(H, 256)), dim3(256), 0, c->stream, hr, sk, H,
+                                   (uint32_t)B.p_read_base, kbits);
+            });
+            c->check_launch("lk_rebase");
+        }
+        B.hits += H;
+    }
+    HGA_HIP(hipEventRecord(S.ev_free, c->stream));
+    S.used = true;
+    B.pending = false;
+}
+}  // namespace
+
+uint64_t lookup_batch_estimate(uint64_t batch_bases, uint64_t batch_reads) {
+    HGA_REQUIRE(batch_reads <= lksizing::kMaxReads, HGA_ERR_INVALID, "too many reads");
+    HGA_REQUIRE(batch_bases < (1ull << 56), HGA_ERR_INVALID, "too many bases");
+    return lksizing::slot_bytes(batch_bases, batch_reads);
+}
+
+void lookup_abandon(hga_ctx* c) {
+    auto& B = c->lookup.batch;
+    if (!B.open) return;
+    batch_join(c);
+    B.open = false;
+    B.pending = false;
+}
+
+void lookup_begin(hga_ctx* c, uint32_t first_id) {
+    auto& L = c->lookup;
+    auto& B = L.batch;
+    HGA_REQUIRE(L.loaded, HGA_ERR_STATE, "hga_lookup_load not called");
+    lookup_abandon(c);
+    c->sync();   // the one-shot buffers released below may still be read by an earlier call's kernels
+    c->conn.ready = false;
+    c->forest.have = false;
+    L.gathered = false;
+    L.ran = false;
+    L.have_reads = false;
+    L.packed_ok = false;
+    for (DevBuf* b : {&L.bases, &L.offsets, &L.packed, &L.valid, &L.starts, &L.word_read, &L.win_kid, &L.scratch,
+                      &L.tile_cnt})
+        b->release();
+    L.n_reads = L.n_bases = 0;
+    L.first_read_id = first_id;
+    L.windows = L.hits = L.firsts = L.reads_hit = 0;
+    L.h_offsets.assign(1, 0);
+    (void)c->side_stream();
+    for (auto& s : B.slot) {
+        batch_events(s);
+        s.used = false;
+        *static_cast<unsigned long long*>(s.h_hits.ensure(64)) = 0;
+    }
+    B.next = 0;
+    B.pending = false;
+    B.hits = 0;
+    B.slot_max_bases = B.slot_max_reads = 0;
+    B.stats = hga_lookup_batch_stats{};
+    B.stats.slot_bytes = 0;
+    for (auto& s : B.slot) B.stats.slot_bytes += s.dev.p ? s.dev.cap : 0;   // (slots of an earlier session stay)
+    B.open = B.ever = true;
+}
+
+void lookup_add_reads(hga_ctx* c, const char* bases, const uint64_t* offsets, uint64_t n) {
+    auto& L = c->lookup;
+    auto& B = L.batch;
+    HGA_REQUIRE(B.open, HGA_ERR_STATE, "hga_lookup_begin not called");
+    HGA_REQUIRE(n < (1ull << 32) && L.n_reads + n < (1ull << 32), HGA_ERR_INVALID, "too many reads");
+    HGA_REQUIRE(offsets[0] == 0 || n == 0, HGA_ERR_INVALID, "offsets[0] must be 0");
+    for (uint64_t i = 0; i < n; ++i)
+        HGA_REQUIRE(offsets[i + 1] >= offsets[i], HGA_ERR_INVALID, "offsets must be non-decreasing");
+    const uint64_t nb = n ? offsets[n] - offsets[0] : 0;
+    const lksizing::Slot need = lksizing::slot(nb, n);
+    try {
+        if (need.n_tiles) {
+            auto& S = B.slot[B.next & 1];
+            // the slot's last batch is either the pending one (a slot count of one would need this) or emitted
+            if (B.pending && B.p_slot == (int)(B.next & 1)) batch_emit_pending(c);
+            // a slot is cut for the largest batch the session has seen (bases and reads) when it is next used
+            B.slot_max_bases = std::max(B.slot_max_bases, nb);
+            B.slot_max_reads = std::max(B.slot_max_reads, n);
+            if (B.slot_max_bases > S.cap_bases || B.slot_max_reads > S.cap_reads || !S.dev.p) {
+                // a larger slot: its last reader must be done before the old allocation goes
+                if (S.used) HGA_HIP(hipEventSynchronize(S.ev_free));
+                const uint64_t cb = std::max(B.slot_max_bases, S.cap_bases), cr = std::max(B.slot_max_reads, S.cap_reads);
+                const lksizing::Slot z = lksizing::slot(cb, cr);
+                B.stats.slot_bytes -= S.dev.p ? S.dev.cap : 0;
+                S.dev.release();
+                S.cap_bases = S.cap_reads = 0;
+                S.dev.ensure(z.bytes);
+                S.stage.ensure(z.stage_bytes);
+                S.cap_bases = cb;
+                S.cap_reads = cr;
+                B.stats.slot_bytes += S.dev.cap;
+            }
+            const lksizing::Slot z = lksizing::slot(S.cap_bases, S.cap_reads);
+            char* d = S.dev.as<char>();
+            char* h = static_cast<char*>(S.stage.p);
+            std::memcpy(h, bases, nb);
+            std::memcpy(h + z.o_stage_offsets, offsets, (n + 1) * 8);
+            hipStream_t up = c->side_stream();
+            if (S.used) HGA_HIP(hipStreamWaitEvent(up, S.ev_free, 0));
+            HGA_HIP(hipMemcpyAsync(d + z.o_bases, h, nb, hipMemcpyHostToDevice, up));
+            HGA_HIP(hipMemcpyAsync(d + z.o_offsets, h + z.o_stage_offsets, (n + 1) * 8, hipMemcpyHostToDevice, up));
+            HGA_HIP(hipEventRecord(S.ev_up, up));
+            HGA_HIP(hipStreamWaitEvent(c->stream, S.ev_up, 0));
+            auto* sb = reinterpret_cast<unsigned int*>(d + z.o_starts);
+            auto* wr = reinterpret_cast<uint32_t*>(d + z.o_word_read);
+            auto* offs = reinterpret_cast<const uint64_t*>(d + z.o_offsets);
+            auto* tile = reinterpret_cast<unsigned long long*>(d + z.o_tile);
+            HGA_HIP(hipMemsetAsync(sb, 0, need.b_starts, c->stream));   // the bitmap of this batch's words + pads
+            c->launch("lk_pack", [&] {
+                hipLaunchKernelGGL(lk_read_map, dim3(blocks_for(n, 4)), dim3(256), 0, c->stream, offs, n, nb, sb, wr);
+            });
+            c->check_launch("lk_pack");
+            LkTab tab{L.tab_key.p, L.filter.as<uint32_t>(), L.slots, L.fwords - 1, L.idb,
+                      reinterpret_cast<const uint8_t*>(d + z.o_bases)};
+            static_assert(HGA_LK_ASCII != 0, "a batch slot holds no packed codes: lk_scan packs from the ASCII reads");
+            lookup_count_scan(c, need.n_tiles, nullptr, nullptr, sb, nb, offs, n, wr, tab,
+                              reinterpret_cast<uint32_t*>(d + z.o_hmask), reinterpret_cast<uint32_t*>(d + z.o_win_kid),
+                              tile);
+            HGA_HIP(hipMemsetAsync(tile + need.n_tiles, 0, 8, c->stream));
+            exclusive_scan_u64(c, reinterpret_cast<uint64_t*>(tile), need.n_tiles + 1, L.scratch3);
+            HGA_HIP(hipMemcpyAsync(S.h_hits.p, tile + need.n_tiles, 8, hipMemcpyDeviceToHost, c->stream));
+            HGA_HIP(hipEventRecord(S.ev_cnt, c->stream));
+            // the previous batch: its hit count is long there, its emit queues behind this batch's count scan
+            batch_emit_pending(c);
+            B.pending = true;
+            B.p_slot = (int)(B.next & 1);
+            B.p_reads = n;
+            B.p_bases = nb;
+            B.p_read_base = L.n_reads;
+            B.p_tiles = need.n_tiles;
+            ++B.next;
+        }
+    } catch (...) {
+        // nothing enqueued may outlive the error: the caller's next call may free or rewrite what it reads
+        batch_join(c);
+        B.open = false;
+        B.pending = false;
+        throw;
+    }
+    const int k = L.k;
+    const uint64_t base0 = L.h_offsets.back();
+    L.h_offsets.reserve(L.h_offsets.size() + n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        if (len >= (uint64_t)k) L.windows += len - k + 1;
+        L.h_offsets.push_back(base0 + offsets[i + 1]);
+    }
+    L.n_reads += n;
+    L.n_bases += nb;
+    ++B.stats.batches;
+    B.stats.reads = L.n_reads;
+    B.stats.bases = L.n_bases;
+}
+
+void lookup_finish(hga_ctx* c) {
+    auto& L = c->lookup;
+    auto& B = L.batch;
+    HGA_REQUIRE(B.open, HGA_ERR_STATE, "hga_lookup_begin not called");
+    try {
+        batch_emit_pending(c);
+        const uint64_t H = B.hits;
+        batch_grow_hits(c, H, H);   // (at least one element each, as lookup_run leaves them)
+        uint64_t rb = 0;
+        for (DevBuf* b : {&L.hit_read, &L.hit_kid, &L.hit_pos, &L.s_key, &L.s_val}) rb += b->cap;
+        B.stats.result_bytes = rb;
+        L.hits = H;
+        lookup_build_indices(c, L.n_reads, H);
+    } catch (...) {
+        batch_join(c);
+        B.open = false;
+        B.pending = false;
+        L.ran = false;
+        throw;
+    }
+    batch_join(c);   // the index build has synchronised the ctx stream; this also frees the retired arrays
+    B.open = false;
+}
+
 void lookup_run(hga_ctx* c) {
     auto& L = c->lookup;
     if (L.gathered) {   // back to this rank's own reads (hga_lookup_gather replaced the results)
@@ -1346,27 +1668,7 @@ void lookup_run(hga_ctx* c) {
               HGA_LK_ASCII ? L.bases.as<uint8_t>() : nullptr};
     uint64_t H = 0;
     if (n_tiles) {
-        c->launch("lk_count", [&] {
-#define HGA_LK_SCAN2(KMV, KK, PKV)                                                                           \
-    hipLaunchKernelGGL((lk_scan<false, KMV, KK, PKV>), dim3((unsigned)n_tiles), dim3(LK_T), 0, c->stream, pk, vd, \
-                       sb, nb, offs, n, k, L.word_read.as<uint32_t>(), tab, hm, wkid, tile, (uint32_t*)nullptr,  \
-                       (uint32_t*)nullptr, (uint32_t*)nullptr)
-#define HGA_LK_SCAN(KMV, KK)                       \
-    do {                                           \
-        if (L.idb) HGA_LK_SCAN2(KMV, KK, true);    \
-        else HGA_LK_SCAN2(KMV, KK, false);         \
-    } while (0)
-            if (L.km == LK_KM && k == 19) HGA_LK_SCAN(LK_KM, 19);   // compile-time k for the usual SDK k
-            else if (L.km == LK_KM && k == 21) HGA_LK_SCAN(LK_KM, 21);
-            else if (L.km == LK_KM) HGA_LK_SCAN(LK_KM, 0);
-            else if (L.km == 6) HGA_LK_SCAN(6, 17);   // k = 17
-            else if (L.km == 5) HGA_LK_SCAN(5, 16);
-            else if (L.km == 4) HGA_LK_SCAN(4, 15);
-            else HGA_LK_SCAN(0, 0);
-#undef HGA_LK_SCAN
-#undef HGA_LK_SCAN2
-        });
-        c->check_launch("lk_count");
+        lookup_count_scan(c, n_tiles, pk, vd, sb, nb, offs, n, L.word_read.as<uint32_t>(), tab, hm, wkid, tile);
         HGA_HIP(hipMemsetAsync(tile + n_tiles, 0, 8, c->stream));
         exclusive_scan_u64(c, reinterpret_cast<uint64_t*>(tile), n_tiles + 1, L.scratch3);
         HGA_HIP(hipMemcpyAsync(&H, tile + n_tiles, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1387,6 +1689,18 @@ void lookup_run(hga_ctx* c) {
         });
         c->check_launch("lk_emit");
     }
+    lookup_build_indices(c, n, H);
+}
+
+// The second half of a lookup, shared by hga_lookup_run and hga_lookup_finish: every index over the H
+// read-ordered hits of n reads in hit_read / hit_kid / hit_pos / s_key / s_val (read indices 0..n-1).
+static void lookup_build_indices(hga_ctx* c, uint64_t n, uint64_t H) {
+    auto& L = c->lookup;
+    uint32_t* hr = L.hit_read.as<uint32_t>();
+    uint32_t* hk = L.hit_kid.as<uint32_t>();
+    uint64_t* sk = L.s_key.as<uint64_t>();
+    uint32_t* sv = L.s_val.as<uint32_t>();
+    const int kbits = bits_for(std::max<uint32_t>(L.n_sdk, 1));
     // kmer_component_index (ReadClusteringEngine.cpp:262-267, 282-284), from the read-ordered hits
     bool kjoin = false;
     uint64_t* kptr = static_cast<uint64_t*>(L.kci_ptr.ensure(((uint64_t)L.n_sdk + 1) * 8));

@@ -45,6 +45,11 @@ class LookupSizes(C.Structure):
                 ("firsts", C.c_uint64), ("reads_hit", C.c_uint64), ("n_sdk", C.c_uint32)]
 
 
+class LookupBatchStats(C.Structure):   # hga_lookup_batch_stats
+    _fields_ = [("batches", C.c_uint64), ("reads", C.c_uint64), ("bases", C.c_uint64), ("slot_bytes", C.c_uint64),
+                ("result_bytes", C.c_uint64), ("regrowths", C.c_uint64), ("host_waits", C.c_uint64)]
+
+
 class ComponentsSizes(C.Structure):
     _fields_ = [("index_entries", C.c_uint64), ("survivors", C.c_uint64), ("survivor_kmers", C.c_uint64),
                 ("merges", C.c_uint64)]
@@ -107,6 +112,11 @@ HGA_SYMBOLS = {
     "hga_lookup_load": (C.c_int, [_vp, C.c_int, _u64p, C.c_uint32]),
     "hga_lookup_set_reads": (C.c_int, [_vp, C.c_char_p, _u64p, C.c_uint64, C.c_uint32]),
     "hga_lookup_run": (C.c_int, [_vp]),
+    "hga_lookup_begin": (C.c_int, [_vp, C.c_uint32]),
+    "hga_lookup_add_reads": (C.c_int, [_vp, C.c_char_p, _u64p, C.c_uint64]),
+    "hga_lookup_finish": (C.c_int, [_vp]),
+    "hga_lookup_batch_estimate": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u64p]),
+    "hga_lookup_get_batch_stats": (C.c_int, [_vp, C.POINTER(LookupBatchStats)]),
     "hga_lookup_get_sizes": (C.c_int, [_vp, C.POINTER(LookupSizes)]),
     "hga_lookup_fetch": (C.c_int, [_vp, C.POINTER(LookupResult)]),
     "hga_connections_run": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint32, C.c_uint64, _i32p, _u64p]),
@@ -444,6 +454,28 @@ class Ctx:
 
     def lookup_run(self):
         _ck(lib().hga_lookup_run(self._h))
+
+    # the lookup in read batches: begin, add_reads per batch (a CSR of whole reads), finish
+    def lookup_begin(self, first_read_id: int = 1):
+        _ck(lib().hga_lookup_begin(self._h, first_read_id))
+
+    def lookup_add_reads(self, bases: bytes, offsets):
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        _ck(lib().hga_lookup_add_reads(self._h, bases, _p(off, C.c_uint64), len(off) - 1))
+
+    def lookup_finish(self):
+        _ck(lib().hga_lookup_finish(self._h))
+
+    def lookup_batch_estimate(self, batch_bases: int, batch_reads: int) -> int:
+        """Device bytes of a session's two slots for batches of at most this size (host arithmetic)."""
+        b = C.c_uint64()
+        _ck(lib().hga_lookup_batch_estimate(self._h, batch_bases, batch_reads, C.byref(b)))
+        return b.value
+
+    def lookup_batch_stats(self) -> LookupBatchStats:
+        s = LookupBatchStats()
+        _ck(lib().hga_lookup_get_batch_stats(self._h, C.byref(s)))
+        return s
 
     def lookup_sizes(self) -> LookupSizes:
         s = LookupSizes()

@@ -4,6 +4,7 @@
 // switches, and an "unrecognised option" error for anything else.
 #pragma once
 
+#include <cstdint>
 #include <cstdio>
 #include <functional>
 #include <map>
@@ -12,6 +13,26 @@
 #include <vector>
 
 namespace hgah {
+
+// The argument of a size option such as "--mem-budget": a number with an optional K / M / G suffix (powers
+// of 1024).  `option` is the option's long name, for the error text.
+inline uint64_t parse_bytes(const std::string& v, const std::string& option) {
+    const std::string bad = "the argument ('" + v + "') for option '--" + option + "' is invalid";
+    size_t pos = 0;
+    unsigned long long n = 0;
+    try {
+        n = std::stoull(v, &pos);
+    } catch (const std::exception&) {   // no number at all, or one past 64 bits
+        throw std::invalid_argument(bad);
+    }
+    unsigned shift = 0;
+    if (pos < v.size()) {
+        const char u = v[pos];
+        shift = u == 'K' || u == 'k' ? 10 : u == 'M' || u == 'm' ? 20 : u == 'G' || u == 'g' ? 30 : 64;
+        if (shift == 64 || pos + 1 != v.size() || (n >> (64 - shift)) != 0) throw std::invalid_argument(bad);
+    }
+    return (uint64_t)n << shift;
+}
 
 struct ArgSpec {
     std::string longname;   // without "--"

@@ -21,6 +21,10 @@
 // (ranks.h).  Every rank loads the whole SDK set and looks up a contiguous ReadID range of the
 // reads; hga_lookup_gather gives every rank the whole input's index; the device connection pass
 // splits its pivots over the ranks and hga_connections_gather joins them in the reference order.
+//
+// --read-batch SIZE (extension, off by default): every rank feeds its share of the loaded reads to the lookup
+// in batches of at most SIZE bases (whole reads, at least one), so the scan's device memory follows SIZE.  The
+// files are still read whole first; the output is that of a run without the option.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -94,6 +98,15 @@ int main(int argc, char* argv[]) {
     int gpus = 1;
     ap.add("gpus", 0, false, "GPUs for the lookup and the first connection pass, one rank each (MI355X build "
            "extension; default 1)", [&](const std::string& v) { gpus = std::stoi(v); });
+    // the lookup in read batches (hga_lookup_begin / _add_reads / _finish): the scan's device memory follows
+    // the batch, not the read set; 0 = off (hga_lookup_set_reads + hga_lookup_run on a rank's whole share)
+    uint64_t read_batch = 0;
+    ap.add("read-batch", 0, false, "Look the reads up in batches of this many bases, suffix K/M/G (MI355X build "
+           "extension; default: all at once)", [&](const std::string& v) {
+               read_batch = hgah::parse_bytes(v, "read-batch");
+               if (read_batch == 0)
+                   throw std::invalid_argument("the argument ('" + v + "') for option '--read-batch' is invalid");
+           });
     ap.parse(argc, argv);
     for (auto& p : ap.positional) read_paths.push_back(p);
     if (ap.has("help")) {
@@ -142,9 +155,31 @@ int main(int argc, char* argv[]) {
         std::vector<uint64_t> offs(rs.offsets.begin() + (int64_t)a, rs.offsets.begin() + (int64_t)b + 1);
         for (auto& o : offs) o -= rs.offsets[a];
         check(hga_lookup_load(c, k, kk.first.data(), (uint32_t)kk.first.size()), "hga_lookup_load");
-        check(hga_lookup_set_reads(c, rs.bases.data() + rs.offsets[a], offs.data(), b - a, (uint32_t)(1 + a)),
-              "hga_lookup_set_reads");
-        check(hga_lookup_run(c), "hga_lookup_run");
+        if (read_batch) {
+            // batches cut at read boundaries: as many whole reads as fit in read_batch bases, at least one
+            check(hga_lookup_begin(c, (uint32_t)(1 + a)), "hga_lookup_begin");
+            std::vector<uint64_t> boffs;
+            for (uint64_t i = 0, n = b - a; i < n;) {
+                uint64_t j = i + 1;
+                while (j < n && offs[j + 1] - offs[i] <= read_batch) ++j;
+                boffs.assign(offs.begin() + (int64_t)i, offs.begin() + (int64_t)j + 1);
+                for (auto& o : boffs) o -= offs[i];
+                check(hga_lookup_add_reads(c, rs.bases.data() + rs.offsets[a] + offs[i], boffs.data(), j - i),
+                      "hga_lookup_add_reads");
+                i = j;
+            }
+            check(hga_lookup_finish(c), "hga_lookup_finish");
+            if (tm.on && r == 0) {
+                hga_lookup_batch_stats bs;
+                check(hga_lookup_get_batch_stats(c, &bs), "hga_lookup_get_batch_stats");
+                std::fprintf(stderr, "hga-timing lookup.batches %llu\nhga-timing lookup.slot_bytes %llu\n",
+                             (unsigned long long)bs.batches, (unsigned long long)bs.slot_bytes);
+            }
+        } else {
+            check(hga_lookup_set_reads(c, rs.bases.data() + rs.offsets[a], offs.data(), b - a, (uint32_t)(1 + a)),
+                  "hga_lookup_set_reads");
+            check(hga_lookup_run(c), "hga_lookup_run");
+        }
         if (P > 1) check(hga_lookup_gather(c), "hga_lookup_gather");   // every rank: the whole index
     });
     hga_lookup_sizes sz;

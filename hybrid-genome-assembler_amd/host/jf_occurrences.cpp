@@ -65,20 +65,6 @@ using hgah::PhaseTimer;
 
 using KmerSpecificity = std::map<double, std::map<int, int>>;
 
-// "--mem-budget": bytes, with an optional K / M / G suffix (powers of 1024)
-uint64_t parse_bytes(const std::string& v) {
-    size_t pos = 0;
-    const unsigned long long n = std::stoull(v, &pos);
-    unsigned shift = 0;
-    if (pos < v.size()) {
-        const char u = v[pos];
-        shift = u == 'K' || u == 'k' ? 10 : u == 'M' || u == 'm' ? 20 : u == 'G' || u == 'g' ? 30 : 64;
-        if (shift == 64 || pos + 1 != v.size() || (n >> (64 - shift)) != 0)
-            throw std::invalid_argument("the argument ('" + v + "') for option '--mem-budget' is invalid");
-    }
-    return (uint64_t)n << shift;
-}
-
 // plot_kmer_specificity (src/common/Plotting.cpp:20-37)
 std::string plot_wire(const std::map<int, KmerSpecificity>& specs, int max_coverage) {
     std::string ks;
@@ -126,7 +112,7 @@ int main(int argc, char* argv[]) {
     ap.add("passes", 0, false, "Count in this many key-range passes (MI355X build extension; default: as many as the memory needs)",
            [&](const std::string& v) { passes = (uint32_t)std::stoul(v); });
     ap.add("mem-budget", 0, false, "Device bytes the count may use, suffix K/M/G (MI355X build extension; default: the free memory)",
-           [&](const std::string& v) { mem_budget = parse_bytes(v); });
+           [&](const std::string& v) { mem_budget = hgah::parse_bytes(v, "mem-budget"); });
     ap.parse(argc, argv);
     for (auto& p : ap.positional) read_paths.push_back(p);
     if (ap.has("help")) {

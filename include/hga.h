@@ -296,6 +296,46 @@ typedef struct hga_lookup_result {
 } hga_lookup_result;
 hga_status hga_lookup_fetch(hga_ctx* ctx, const hga_lookup_result* out);
 
+/* The lookup in read batches: the same result as hga_lookup_set_reads + hga_lookup_run on the
+ * concatenated reads, with the scan's device memory (about 5.5 B per base one-shot) bounded by the
+ * largest batch instead of the read set.  After hga_lookup_finish every consumer of a lookup result
+ * (hga_lookup_get_sizes / _fetch / _gather, hga_connections_*, hga_components_*, hga_spanning_forest*,
+ * hga_tree_tails, hga_read_overlaps, hga_connections_quality) works as after hga_lookup_run.
+ *
+ * hga_lookup_begin opens a session (HGA_ERR_STATE before hga_lookup_load); it invalidates what
+ * hga_lookup_run invalidates and releases the read buffers of an earlier hga_lookup_set_reads.  A second
+ * begin abandons the open session and starts again.
+ * hga_lookup_add_reads appends a CSR of whole reads (offsets[0] == 0, non-decreasing, as
+ * hga_lookup_set_reads): read i of this call has ReadID first_read_id + (reads added before) + i; all
+ * reads of a session number fewer than 2^32.  A batch of no reads, of empty reads only, or without a
+ * hit is legal.  On return the caller's buffers may be reused; the batch's kernels need not have
+ * finished, and an error of theirs is reported by a later hga_lookup_add_reads or by hga_lookup_finish.
+ * hga_lookup_finish builds the indices over all hits and closes the session.  No reads stay resident:
+ * hga_hll_registers and hga_lookup_run return HGA_ERR_STATE until the next hga_lookup_set_reads.
+ * While a session is open, hga_lookup_run / _fetch / _get_sizes / _gather / _load, hga_hll_registers and
+ * every consumer of a lookup result return HGA_ERR_STATE (the message names the open session);
+ * hga_lookup_set_reads abandons the session and returns to the one-shot path.
+ *
+ * Device memory of a session: two slots sized by the largest batch seen (hga_lookup_batch_estimate:
+ * host arithmetic only, their bytes for batches of at most batch_bases bases and batch_reads reads),
+ * and the hit arrays (24 B per hit), grown geometrically with their contents kept. */
+hga_status hga_lookup_begin(hga_ctx* ctx, uint32_t first_read_id);
+hga_status hga_lookup_add_reads(hga_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_reads);
+hga_status hga_lookup_finish(hga_ctx* ctx);
+hga_status hga_lookup_batch_estimate(hga_ctx* ctx, uint64_t batch_bases, uint64_t batch_reads,
+                                     uint64_t* slot_bytes);
+typedef struct hga_lookup_batch_stats {
+    uint64_t batches;       /* hga_lookup_add_reads calls of the session                          */
+    uint64_t reads;
+    uint64_t bases;
+    uint64_t slot_bytes;    /* device bytes allocated for both slots at the largest batch seen   */
+    uint64_t result_bytes;  /* device bytes of the appended hit arrays (their capacity)          */
+    uint64_t regrowths;     /* times the hit arrays were replaced by larger ones, contents kept  */
+    uint64_t host_waits;    /* times the host waited for a batch's hit count                     */
+} hga_lookup_batch_stats;
+/* The open session so far, or the last finished one (HGA_ERR_STATE before any hga_lookup_begin). */
+hga_status hga_lookup_get_batch_stats(hga_ctx* ctx, hga_lookup_batch_stats* out);
+
 /* Sharded lookup on a ctx with a communicator: every rank loads the same
  * SDK set (hga_lookup_load), sets its contiguous ReadID range of the reads (hga_lookup_set_reads with
  * first_read_id = the range's first ReadID, ranks in ReadID order) and runs hga_lookup_run; then
