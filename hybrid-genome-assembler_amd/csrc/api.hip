@@ -133,6 +133,16 @@ hga_status hga_count_add(hga_ctx* c, uint32_t file, const char* seq, uint64_t n_
     });
 }
 
+hga_status hga_count_add_file(hga_ctx* c, uint32_t file, const char* bytes, uint64_t n_bytes, hga_ingest_info* info) {
+    HGA_CTX_GUARD(c, hga::count_add_file(c, file, bytes, n_bytes, info));
+}
+
+hga_status hga_count_seq(hga_ctx* c, uint32_t file, char** bytes, uint64_t* n) {
+    HGA_CTX_GUARD(c, hga::count_seq(c, file, bytes, n));
+}
+
+uint32_t hga_ingest_tile(void) { return hga::ingest_tile(); }
+
 hga_status hga_connections_run(hga_ctx* c, const uint32_t* pivots, uint64_t n_pivots, uint32_t min_kmers,
                                uint64_t min_score, const int32_t* categories, uint64_t* n) {
     HGA_RESULT_GUARD(c, "hga_connections_run", {

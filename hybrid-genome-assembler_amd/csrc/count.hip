@@ -2548,6 +2548,7 @@ void count_run(hga_ctx* c, uint32_t min_per_file) {
     // A previous run nobody consumed is discarded, errors included: this run replaces its rows
     // (the stream is in order, and kc_init_stat re-initialises the counters it would have read).
     s.pending = false;
+    ingest_release(c);   // hga_count_add_file's staging goes before this run's buffers are sized and allocated
     const uint32_t F = s.n_files;
     s.min_per_file = min_per_file;
     // every size-derived choice (count_sizing.hpp): one pass as ever, or P key-range passes

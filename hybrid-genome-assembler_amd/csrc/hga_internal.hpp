@@ -200,6 +200,9 @@ struct CountState {
     uint32_t cfg_passes = 0, run_passes = 1;
     uint64_t cfg_budget = 0, run_budget = 0, work_bytes = 0, pass_max = 0, pass_min = 0;
     DevBuf pass_cum;   // instances of passes 0..p (P - 1 running sums, kc_pass_next)
+    // hga_count_add_file (ingest.hip): the raw bytes of one call, their line starts, the per-tile newline and
+    // kept-byte counts and the control words; grow-only across calls, released by hga_count_run
+    DevBuf ing_raw, ing_st, ing_cnt, ing_kept, ing_ctl;
     bool dist = false;      // rows are this rank's owner range after hga_count_exchange
     ~CountState() {
         for (auto* b : seq) delete b;
@@ -416,6 +419,12 @@ namespace hga {
 void count_begin(hga_ctx* c, int k, uint32_t n_files);
 void count_add(hga_ctx* c, uint32_t file, const char* seq, uint64_t n);
 void count_run(hga_ctx* c, uint32_t min_per_file);
+// ingest.hip: a FASTA / FASTQ file's raw bytes parsed into seq[file] on the device (hga_count_add_file), the
+// resident stream of a file copied out, the input bytes per workgroup, and the parser's buffers given back
+void count_add_file(hga_ctx* c, uint32_t file, const char* bytes, uint64_t n, hga_ingest_info* info);
+void count_seq(hga_ctx* c, uint32_t file, char** bytes, uint64_t* n);
+uint32_t ingest_tile();
+void ingest_release(hga_ctx* c);
 // key-range passes (count.hip): the setting, and the bytes count_run would request under it
 void count_set_passes(hga_ctx* c, uint32_t passes, uint64_t budget);
 uint64_t count_estimate(hga_ctx* c, uint32_t min_per_file, uint32_t passes);

@@ -60,6 +60,11 @@ class TreeEnds(C.Structure):   # hga_tree_ends
                 ("left_dist", C.c_uint64)]
 
 
+class IngestInfo(C.Structure):
+    _fields_ = [("layout", C.c_uint32), ("reserved", C.c_uint32), ("records", C.c_uint64), ("lines", C.c_uint64),
+                ("seq_bytes", C.c_uint64)]
+
+
 class LookupResult(C.Structure):
     _fields_ = [("hit_ptr", _u64p), ("hit_kid", _u32p), ("hit_pos", _u32p), ("sorted_kid", _u32p),
                 ("first_ptr", _u64p), ("first_kid", _u32p), ("first_pos", _u32p),
@@ -91,6 +96,9 @@ HGA_SYMBOLS = {
     "hga_ctx_destroy": (C.c_int, [_vp]),
     "hga_count_begin": (C.c_int, [_vp, C.c_int, C.c_uint32]),
     "hga_count_add": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_uint64]),
+    "hga_count_add_file": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(IngestInfo)]),
+    "hga_count_seq": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p]),
+    "hga_ingest_tile": (C.c_uint32, []),
     "hga_count_add_rows": (C.c_int, [_vp, C.c_uint32, _u64p, _u32p, C.c_uint64]),
     "hga_count_run": (C.c_int, [_vp, C.c_uint32]),
     "hga_count_get_stats": (C.c_int, [_vp, C.POINTER(CountStats)]),
@@ -175,6 +183,7 @@ HOST_SYMBOLS = {
                                    C.POINTER(_i32p), C.POINTER(_u32p), C.POINTER(_u32p), _u64p,
                                    C.POINTER(_u64p), C.POINTER(_vp)]),
     "hgh_jf_stream": (C.c_int, [C.c_char_p, C.POINTER(_vp), _u64p, _u64p]),
+    "hgh_cut_records": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, C.POINTER(_u64p), _u64p]),
     "hgh_fmt_double": (C.c_int, [C.c_double, C.c_char_p, C.c_int]),
     "hgh_hll_estimate": (C.c_double, [_u8p, C.c_int]),
     "hgh_set_threads": (None, [C.c_int]),
@@ -335,6 +344,23 @@ class Ctx:
 
     def count_add(self, file: int, seq: bytes):
         _ck(lib().hga_count_add(self._h, file, seq, len(seq)))
+
+    def count_add_file(self, file: int, data: bytes) -> dict:
+        """The raw bytes of a FASTA / FASTQ file (or a piece cut at a record start, cut_records), parsed on
+        the device into the file's stream (hga_count_add_file).  Returns layout (0 empty, 1 FASTA, 2 FASTQ,
+        3 refused: nothing added, parse on the host), records, lines and seq_bytes."""
+        info = IngestInfo()
+        _ck(lib().hga_count_add_file(self._h, file, data, len(data), C.byref(info)))
+        return {"layout": info.layout, "records": info.records, "lines": info.lines, "seq_bytes": info.seq_bytes}
+
+    def count_seq(self, file: int) -> bytes:
+        """The resident stream of a file, as count_add / count_add_file left it."""
+        p, n = _vp(), C.c_uint64()
+        _ck(lib().hga_count_seq(self._h, file, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            lib().hga_free(p)
 
     def count_add_rows(self, file: int, keys, counts):
         """Rows of a cached `<reads>_<k>-mers_sorted` dump for `file` (summed in verbatim)."""
@@ -836,6 +862,19 @@ def load_records(paths, annotate: bool):
         "end": _take(ep, nr, np.uint32, host().hgh_free),
         "meta": meta, "filename": fname,
     }
+
+
+def ingest_tile() -> int:
+    """Input bytes per workgroup of hga_count_add_file's kernels."""
+    return int(lib().hga_ingest_tile())
+
+
+def cut_records(data: bytes, piece: int) -> np.ndarray:
+    """Piece starts of a FASTA / FASTQ file for Ctx.count_add_file: 0, then the first record start at or
+    after each multiple of `piece` (seqio.h cut_records)."""
+    p, n = _u64p(), C.c_uint64()
+    _hck(host().hgh_cut_records(data, len(data), piece, C.byref(p), C.byref(n)))
+    return _take(p, n.value, np.uint64, host().hgh_free)
 
 
 def jf_stream(path: str) -> bytes:

@@ -102,34 +102,6 @@ void par_for(size_t n, int T, F&& f) {
     for (auto& x : th) x.join();
 }
 
-// A read-only private mapping of a whole file, pages populated up front (page-cache speed, no
-// copy).  Empty files map nothing.
-struct MappedFile {
-    const char* p = nullptr;
-    size_t n = 0;
-    explicit MappedFile(const std::string& path) {
-        const int fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) throw std::invalid_argument("File with path \"" + path + "\" does not exist");
-        const off_t sz = ::lseek(fd, 0, SEEK_END);
-        if (sz > 0) {
-            void* m = ::mmap(nullptr, (size_t)sz, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
-            if (m == MAP_FAILED) {
-                ::close(fd);
-                throw std::runtime_error("cannot map " + path);
-            }
-            (void)::madvise(m, (size_t)sz, MADV_SEQUENTIAL);
-            p = static_cast<const char*>(m);
-            n = (size_t)sz;
-        }
-        ::close(fd);
-    }
-    ~MappedFile() {
-        if (p) ::munmap(const_cast<char*>(p), n);
-    }
-    MappedFile(const MappedFile&) = delete;
-    MappedFile& operator=(const MappedFile&) = delete;
-};
-
 // Calls f(position) for every '\n' in [b, e), in order (16 bytes per SSE2 compare).
 template <class F>
 inline void each_newline(const char* base, size_t b, size_t e, F&& f) {
@@ -271,6 +243,26 @@ bool jf_stream_fast(const char* d, size_t n, int T, Bytes& out, uint64_t* n_reco
 
 }  // namespace
 
+MappedFile::MappedFile(const std::string& path) {
+    const int fd = ::open(path.c_str(), O_RDONLY);
+    if (fd < 0) throw std::invalid_argument("File with path \"" + path + "\" does not exist");
+    const off_t sz = ::lseek(fd, 0, SEEK_END);
+    if (sz > 0) {
+        void* m = ::mmap(nullptr, (size_t)sz, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
+        if (m == MAP_FAILED) {
+            ::close(fd);
+            throw std::runtime_error("cannot map " + path);
+        }
+        (void)::madvise(m, (size_t)sz, MADV_SEQUENTIAL);
+        p = static_cast<const char*>(m);
+        n = (size_t)sz;
+    }
+    ::close(fd);
+}
+MappedFile::~MappedFile() {
+    if (p) ::munmap(const_cast<char*>(p), n);
+}
+
 int host_threads() {
     int t = g_threads.load();
     if (t > 0) return t;
@@ -289,6 +281,45 @@ Bytes jf_stream(const std::string& path, uint64_t* n_records) {
         if (jf_stream_fast(m.p, m.n, T, out, n_records)) return out;
     }
     return jf_stream_seq(path, n_records);
+}
+
+Bytes jf_stream_mem(const char* d, size_t n, uint64_t* n_records) {
+    const int T = host_threads();
+    Bytes out;
+    if (T > 1 && jf_stream_fast(d, n, T, out, n_records)) return out;
+    return jf_stream_mem_seq(d, n, n_records);
+}
+
+std::vector<uint64_t> cut_records(const char* d, size_t n, size_t piece) {
+    if (piece == 0) throw std::invalid_argument("cut_records: the piece size must be positive");
+    std::vector<uint64_t> out{0};
+    size_t q = 0;
+    while (q < n && d[q] == '\n') ++q;
+    if (q == n || (d[q] != '>' && d[q] != '@')) return out;
+    const bool fastq = d[q] == '@';
+    // the start of the line behind the one that starts at b (n: none)
+    auto next_line = [&](size_t b) -> size_t {
+        if (b >= n) return n;
+        const void* nl = std::memchr(d + b, '\n', n - b);
+        return nl ? (size_t)(static_cast<const char*>(nl) - d) + 1 : n;
+    };
+    auto record_start = [&](size_t b) -> bool {
+        if (!fastq) return d[b] == '>';
+        if (d[b] != '@') return false;
+        const size_t l2 = next_line(next_line(b));
+        return l2 < n && d[l2] == '+';
+    };
+    size_t target = piece;
+    while (target < n) {
+        size_t b = d[target - 1] == '\n' ? target : next_line(target);
+        while (b < n && !record_start(b)) b = next_line(b);
+        if (b >= n) break;
+        if (b > out.back()) out.push_back(b);
+        const size_t m = b / piece + 1;   // the smallest multiple of piece above this start
+        if (m > (SIZE_MAX - piece) / piece) break;
+        target = m * piece;
+    }
+    return out;
 }
 
 RecordSet load_records(const std::vector<std::string>& paths, bool annotate, bool keep_text) {

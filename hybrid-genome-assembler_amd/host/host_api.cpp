@@ -151,6 +151,15 @@ int hgh_jf_stream(const char* path, char** out, uint64_t* len, uint64_t* n_recor
     });
 }
 
+// Piece starts of a FASTA / FASTQ file in memory (seqio.h cut_records), for the tests.
+int hgh_cut_records(const char* d, uint64_t n, uint64_t piece, uint64_t** out, uint64_t* n_out) {
+    return guard([&] {
+        const std::vector<uint64_t> v = hgah::cut_records(d, n, piece);
+        *out = dup(v.data(), v.size());
+        *n_out = v.size();
+    });
+}
+
 int hgh_fmt_double(double v, char* buf, int cap) {
     std::string s = hgah::fmt_double(v);
     if ((int)s.size() + 1 > cap) return -1;

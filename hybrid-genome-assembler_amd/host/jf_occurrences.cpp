@@ -31,6 +31,13 @@
 // contiguous share of every file's reads with min 1; hga_count_exchange moves the rows to their owner
 // ranks (RCCL over xGMI, or a host transport when ranks share a GPU) and applies the --bc drop; the
 // histogram, dumps and export are then the whole input's, written by rank 0 exactly as with one GPU.
+//
+// --device-parse (extension, off by default): a read file without a dump cache is not parsed on the host.
+// It is mapped, cut at record starts into pieces of HGA_INGEST_PIECE bytes (default 1G; K/M/G suffixes) and
+// each piece handed to hga_count_add_file as it lies in the mapping.  From the first piece the device
+// refuses (a layout that is not line-local) or that is longer than 2^32 - 1 bytes, the rest of the file is
+// parsed on the host as ever: the accepted prefix ends between records, where the sequential parser is in
+// its initial state.  One GPU only.  Every output is byte-identical to a run without the option.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -113,6 +120,7 @@ int main(int argc, char* argv[]) {
            [&](const std::string& v) { passes = (uint32_t)std::stoul(v); });
     ap.add("mem-budget", 0, false, "Device bytes the count may use, suffix K/M/G (MI355X build extension; default: the free memory)",
            [&](const std::string& v) { mem_budget = hgah::parse_bytes(v, "mem-budget"); });
+    ap.add("device-parse", 0, true, "Parse FASTA / FASTQ on the GPU instead of the host (MI355X build extension; one GPU)", nullptr);
     ap.parse(argc, argv);
     for (auto& p : ap.positional) read_paths.push_back(p);
     if (ap.has("help")) {
@@ -120,6 +128,12 @@ int main(int argc, char* argv[]) {
         return 0;
     }
     if (read_paths.empty()) throw std::invalid_argument("You need to specify paths to read files");
+    const bool device_parse = ap.has("device-parse");
+    if (device_parse && gpus > 1)
+        throw std::invalid_argument("--device-parse parses on one GPU; it cannot be combined with --gpus");
+    uint64_t ingest_piece = 1ull << 30;
+    if (const char* e = std::getenv("HGA_INGEST_PIECE")) ingest_piece = hgah::parse_bytes(e, "device-parse (HGA_INGEST_PIECE)");
+    if (device_parse && ingest_piece == 0) throw std::invalid_argument("HGA_INGEST_PIECE must be positive");
 
     PhaseTimer tm;
     const char* dev_env = std::getenv("HGA_DEVICE");
@@ -157,7 +171,7 @@ int main(int argc, char* argv[]) {
             cached[f] = true;
             continue;
         }
-        streams[f] = hgah::jf_stream(read_paths[f]);
+        if (!device_parse) streams[f] = hgah::jf_stream(read_paths[f]);
         counted.push_back(f);
     }
     tm.mark("read_files");
@@ -172,12 +186,32 @@ int main(int argc, char* argv[]) {
         // as the reference's single export pass writes them, JellyfishOccurrenceReader.cpp:110-135)
         if (P > 1) check(hga_comm_set_root(c, 0), "hga_comm_set_root");
     }
+    uint64_t ingest_pieces = 0, ingest_device = 0, ingest_fallback = 0;   // --device-parse
     for (uint32_t f = 0; f < read_paths.size(); ++f) {
         if (cached[f]) {
             check(hga_count_add_rows(ctx, f, cache_k[f].data(), cache_c[f].data(), cache_k[f].size()),
                   "hga_count_add_rows");
             std::vector<uint64_t>().swap(cache_k[f]);
             std::vector<uint32_t>().swap(cache_c[f]);
+            continue;
+        }
+        if (device_parse) {
+            const hgah::MappedFile m(read_paths[f]);
+            const std::vector<uint64_t> cuts = hgah::cut_records(m.p, m.n, ingest_piece);
+            for (size_t i = 0; i < cuts.size(); ++i) {
+                const uint64_t a = cuts[i], b = i + 1 < cuts.size() ? cuts[i + 1] : m.n;
+                hga_ingest_info info{};
+                info.layout = 3;
+                if (b - a <= 0xFFFFFFFFull) check(hga_count_add_file(ctx, f, m.p + a, b - a, &info), "hga_count_add_file");
+                if (info.layout == 3) {   // the rest of the file on the host
+                    const hgah::Bytes rest = hgah::jf_stream_mem(m.p + a, m.n - a);
+                    check(hga_count_add(ctx, f, rest.data(), rest.size()), "hga_count_add");
+                    ingest_fallback += m.n - a;
+                    break;
+                }
+                ++ingest_pieces;
+                ingest_device += b - a;
+            }
             continue;
         }
         const hgah::Bytes& sb = streams[f];
@@ -188,6 +222,9 @@ int main(int argc, char* argv[]) {
         streams[f] = hgah::Bytes();   // freed once uploaded
     }
     tm.mark("upload");
+    if (tm.on && device_parse)
+        std::fprintf(stderr, "hga-timing ingest.pieces %llu\nhga-timing ingest.device_bytes %llu\nhga-timing ingest.host_fallback_bytes %llu\n",
+                     (unsigned long long)ingest_pieces, (unsigned long long)ingest_device, (unsigned long long)ingest_fallback);
     if (P == 1) {
         if (ap.has("passes") || ap.has("mem-budget"))
             check(hga_count_set_passes(ctx, passes, mem_budget), "hga_count_set_passes");

@@ -184,10 +184,18 @@ Bytes jf_stream_seq(const std::string& path, uint64_t* n_records) {
         throw std::runtime_error("short read on " + path);
     }
     std::fclose(f);
+    return jf_stream_mem_seq(data.data(), data.size(), n_records);
+}
+
+Bytes jf_stream_mem_seq(const char* d, size_t n, uint64_t* n_records) {
+    struct {   // (the parser below indexes `data`)
+        const char* p;
+        const char* data() const { return p; }
+        char operator[](size_t j) const { return p[j]; }
+    } data{d};
     Bytes out;
     uint64_t recs = 0;
     size_t i = 0;
-    const size_t n = data.size();
     auto next_line = [&](size_t& b, size_t& e) -> bool {
         if (i >= n) return false;
         b = i;

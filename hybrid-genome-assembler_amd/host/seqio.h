@@ -83,6 +83,30 @@ RecordSet load_records_seq(const std::vector<std::string>& paths, bool annotate,
 // Whole-file read of the sequences jellyfish would count, '\n'-separated.
 Bytes jf_stream(const std::string& path, uint64_t* n_records = nullptr);
 Bytes jf_stream_seq(const std::string& path, uint64_t* n_records = nullptr);
+// The same for bytes in memory: whole records of one file (the whole file, or its rest from a record start).
+Bytes jf_stream_mem(const char* d, size_t n, uint64_t* n_records = nullptr);
+Bytes jf_stream_mem_seq(const char* d, size_t n, uint64_t* n_records = nullptr);
+
+// A read-only private mapping of a whole file, pages populated up front (page-cache speed, no copy).
+// Empty files map nothing.  Throws the readers' "does not exist" error.
+struct MappedFile {
+    const char* p = nullptr;
+    size_t n = 0;
+    explicit MappedFile(const std::string& path);
+    ~MappedFile();
+    MappedFile(const MappedFile&) = delete;
+    MappedFile& operator=(const MappedFile&) = delete;
+};
+
+// Piece starts for parsing a large FASTA / FASTQ file piece by piece (hga_count_add_file takes at most
+// 2^32 - 1 bytes of whole records per call): out[0] = 0, and every later start is the first record start at
+// or after a multiple of `piece` (> 0), strictly ascending.  A record start is a line start whose first byte
+// is '>' (FASTA: the first non-empty line starts with '>'), or a line start with '@' whose line + 2 starts
+// with '+' (FASTQ: it starts with '@').  In 4-line records that is unambiguous: below a quality line that
+// starts with '@', line + 2 is a sequence line, and a sequence line starting with '+' is refused by the
+// device parser anyway.  Any other first byte: the single start 0.  Only the few lines around each cut are
+// looked at.
+std::vector<uint64_t> cut_records(const char* d, size_t n, size_t piece);
 
 // Reader threads: set_host_threads(n > 0) overrides HGA_HOST_THREADS (default min(16, cores));
 // 1 = the sequential readers.

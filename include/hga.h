@@ -67,6 +67,42 @@ hga_status hga_count_begin(hga_ctx* ctx, int k, uint32_t n_files);
  * several times per file; a read must not straddle two calls. */
 hga_status hga_count_add(hga_ctx* ctx, uint32_t file, const char* seq, uint64_t n_bytes);
 
+/* Appends the reads of a FASTA / FASTQ file given as its raw bytes: the file is parsed on the device.
+ * `bytes` holds whole records of one file: the whole file, or a piece cut at a record start; at most
+ * 2^32 - 1 bytes per call (HGA_ERR_INVALID beyond).  What is appended is what jellyfish's reader hands
+ * to the counter for these bytes (`jellyfish count` over the file, src/occurrences/run_jellyfish.sh:3-6):
+ * the sequence of every record, records separated by one '\n'.  Lines are std::getline's ('\n' ends a
+ * line, a last line without one counts, '\r' is an ordinary byte); with `first` the first non-empty line:
+ *   layout 0  no non-empty line: nothing appended, 0 records;
+ *   layout 1  FASTA: `first` starts with '>'.  Every non-empty line starting with '>' is a header (one
+ *             '\n', none for the first), every other line is sequence (its bytes, also when it starts
+ *             with '@' or '+'), empty lines add nothing; records = headers;
+ *   layout 2  FASTQ in 4-line records: `first` is line 0 and starts with '@', the line count is a multiple
+ *             of 4, and every record has an '@' line, a sequence line not starting with '+', a '+' line
+ *             and a quality line as long as the sequence; the sequence lines joined by '\n';
+ *   layout 3  anything else (multi-line FASTQ, ...): nothing is appended, the ctx is exactly as before the
+ *             call, HGA_OK is returned and the caller parses these bytes on the host.
+ * For layouts 0-2 the ctx is left exactly as hga_count_add(the stream of these bytes) would leave it: the
+ * same growth, the same single '\n' between calls.  Calls may be repeated per file and mixed with
+ * hga_count_add and hga_count_add_rows, with or without a communicator.  Synchronous; `bytes` may be
+ * pageable memory and is not read after the return.  The parser's device buffers (the raw bytes and
+ * 4 bytes per line) are kept between calls and released by hga_count_run.
+ * info->lines is filled for every layout, records and seq_bytes (the bytes appended, without the
+ * separator between calls) for layouts 1 and 2.
+ * HGA_ERR_STATE before hga_count_begin; HGA_ERR_INVALID for a bad file index, NULL bytes with
+ * n_bytes > 0, NULL info. */
+typedef struct hga_ingest_info {
+    uint32_t layout;
+    uint32_t reserved;
+    uint64_t records, lines, seq_bytes;
+} hga_ingest_info;
+hga_status hga_count_add_file(hga_ctx* ctx, uint32_t file, const char* bytes, uint64_t n_bytes,
+                              hga_ingest_info* info);
+/* The resident stream of a file, as hga_count_add / hga_count_add_file left it (hga_free). */
+hga_status hga_count_seq(hga_ctx* ctx, uint32_t file, char** bytes, uint64_t* n);
+/* Input bytes per workgroup tile of the parser's kernels (the sizes at which the tests change paths). */
+uint32_t hga_ingest_tile(void);
+
 /* Adds file `file`'s rows from an existing "<reads>_<k>-mers_sorted" dump instead of its
  * reads: the reference skips jellyfish for a file whose dump exists and merges the dump
  * verbatim (src/occurrences/JellyfishOccurrenceReader.cpp:19-24 and the reader's
